@@ -15,6 +15,12 @@ and exits with the child's status.  Every rank checks `WORLD_SIZE == --gpus`.  R
 `--student-fusion` / `--teacher-fusion` select the fusion variants (the reference's ablation sweep,
 train_with_fusion_ablation.py:87-114: concat / minimal / weighted students); the headline workload is
 concat teacher -> weighted student.
+
+A plain run sets up, warms up, times the `--steps` KD steps and prints the headline line (`value`, `ms_per_step`).
+`--full` adds everything else the benchmark measures or checks: the duplicated-batch self-check, the live GEMM
+roofline, the bf16 modes, the fusion-ablation / small-batch side lines, the CPU baseline and (N > 1) the exposed
+all-reduce time; the `--no-*` options switch single pieces of it off.  `--dump-outputs DIR` writes what the last
+timed step returned (losses, student logits, the updated student state) as DIR/<name>.npy, float32.
 """
 import argparse
 import hashlib
@@ -243,6 +249,27 @@ def kernel_code_state():
     return h.hexdigest()[:16]
 
 
+DUMP_MAX_ELEMS = 4 << 20          # per array (16 MB as float32): a larger output is written as a seeded sample of this size
+
+
+def dump_outputs(out_dir, parts, student):
+    """--dump-outputs: what a caller of the timed KD step holds after its last step -- the returned losses and student
+    logits, and the student's updated state (parameters after AdamW, BatchNorm running statistics, state_dict order,
+    concatenated) -- as float32 DIR/<name>.npy.  An array of more than DUMP_MAX_ELEMS elements is written as a fixed,
+    seeded sample of its flattened values (the same indices in every run of the same shape): at most 64 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v for k, v in parts.items() if torch.is_tensor(v)}
+    arrays["student_state"] = torch.cat([v.detach().reshape(-1).float() for v in student.state_dict().values() if v.is_floating_point()])
+    assert sum(4 * min(t.numel(), DUMP_MAX_ELEMS) for t in arrays.values()) <= 64 << 20, {k: t.numel() for k, t in arrays.items()}
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This parent has not touched the
     GPU (torch.cuda.device_count() does not initialise it) and stays a plain parent: no exec, the ranks are children
@@ -331,6 +358,10 @@ def main():
     ap.add_argument("--points-sigma", type=float, default=40.0,
                     help="std (m) of the synthetic x/y coordinates; 40 = the reference's recipe (the headline workload), small "
                          "values pile the points into few BEV cells like the near field of a real sweep (robustness check)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: self-check, roofline, bf16 modes, side benches, CPU baseline, exposed all-reduce time")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step returned (and the updated student state) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-selfcheck", action="store_true")
@@ -344,6 +375,12 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_launches and not args.full:
+        raise SystemExit("--dump-launches writes the roofline's profiled launches: it needs --full")
+    if not args.full:                                         # a plain run: the headline figure only
+        args.no_selfcheck = args.no_roofline = args.no_bf16_forward = args.no_side_benches = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         launch_ranks(args)                                    # never returns
@@ -427,7 +464,7 @@ def main():
         if i == 0:
             first = parts
     barrier()
-    if reducer is not None:
+    if reducer is not None and args.full:
         reducer.exposed = []                                  # event pairs around the waits of finish(): see the `comm` block
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -436,8 +473,10 @@ def main():
             first = parts
     barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, parts, student)
     comm = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         # exposed all-reduce time: how long the COMPUTE stream sat in the waits of reducer.finish() (HIP events recorded on it
         # right before and right after the waits); 0 when the reductions finished under the rest of backward
         ev, reducer.exposed = reducer.exposed, None
@@ -489,7 +528,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             comm["allreduce_exposed_ms_per_step_max_over_ranks"] = round(float(t.item()), 4)
         out["comm"] = comm
-    if world > 1:
+    if world > 1 and args.full:
         out["cpu_baseline"] = None
         out["bf16_forward"] = None
         out["why_null"] = "cpu_baseline / bf16_forward / kd_step_bf16_teacher are measured by the N=1 run only (rank 0, one GPU)"

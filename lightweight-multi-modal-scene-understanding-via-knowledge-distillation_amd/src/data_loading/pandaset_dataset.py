@@ -15,6 +15,7 @@ the device in the consuming process (`DeviceBatchLoader`: one rasteriser launch 
     points       float32 [max_points, 4]  (x, y, z, intensity), zero-padded tail
     segmentation int64   [64, 64]   2-class BEV mask
 """
+import gc
 import os
 from typing import Dict, List, Sequence, Tuple
 
@@ -223,6 +224,16 @@ def _dist_rank_world():
     return 0, 1
 
 
+def _collect_before_fork(loader: DataLoader):
+    """Run the cycle collector HERE before `loader` forks its worker processes.  A forked worker inherits this process's
+    uncollected cyclic garbage (e.g. a finished trainer: its loss criterion closes over it), and its own collector would
+    free it there -- including CUDA tensors that took part in a collective, whose release records HIP events, which a
+    forked child of a process with a HIP context cannot do (the workers died with SIGSEGV at the first epoch of the
+    second fusion variant under torchrun)."""
+    if loader.num_workers > 0:
+        gc.collect()
+
+
 class _EpochLoader:
     """DataLoader + `set_epoch` forwarded to a RankShardSampler (the trainers call it once per epoch)."""
 
@@ -238,6 +249,7 @@ class _EpochLoader:
         return len(self._loader)
 
     def __iter__(self):
+        _collect_before_fork(self._loader)
         return iter(self._loader)
 
 
@@ -269,6 +281,7 @@ class DeviceBatchLoader:
         return len(self._loader)
 
     def __iter__(self):
+        _collect_before_fork(self._loader)
         for raws in self._loader:
             b = self.dataset.prepare_batch(raws)
             if self.to_cpu:                 # for host-side analysis scripts that call .numpy() on the batch tensors

@@ -48,3 +48,38 @@ def test_synthetic_fallback_loader_contract():
     b = next(iter(vl))
     assert b["image"].shape == (2, 3, 256, 256) and b["points"].shape == (2, 5000, 4)
     assert b["segmentation"].shape == (2, 64, 64) and b["segmentation"].dtype == torch.int64
+
+
+def test_loader_frees_cyclic_garbage_before_forking_workers(tmp_path):
+    """Garbage in reference cycles (a finished trainer with its CUDA tensors) must be freed in THIS process before a
+    loader forks its workers: a worker's own collector would free it there, where HIP calls are impossible."""
+    import gc
+    import os
+    from _fake_pandaset import write_tree
+    from src.data_loading.pandaset_dataset import DeviceBatchLoader, PandaSetDataset
+    scenes = write_tree(str(tmp_path / "data"))
+    ds = PandaSetDataset(str(tmp_path / "data"), scenes, max_points=400, verbose=False)
+    ds.prepare_batch = lambda raws: raws                  # host half only: no device stage on this machine
+    log = tmp_path / "freed_by"
+
+    class Cycle:
+        def __init__(self):
+            self.me = self
+
+        def __del__(self):
+            with open(log, "a") as f:
+                f.write(f"{os.getpid()}\n")
+
+    was = gc.isenabled()
+    gc.disable()                                          # no automatic collection: only an explicit one can free it
+    try:
+        Cycle()
+        it = iter(DeviceBatchLoader(ds, batch_size=2, shuffle=False, num_workers=2))
+        batches = [next(it)]                              # the workers have been forked
+        freed_by = log.read_text().split() if log.exists() else []
+        batches += list(it)
+    finally:
+        if was:
+            gc.enable()
+    assert sum(len(b) for b in batches) == len(ds)
+    assert freed_by == [str(os.getpid())]

@@ -89,7 +89,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--points",
-           "2048", "--no-cpu-baseline", "--student-fusion", "minimal"]
+           "2048", "--full", "--no-cpu-baseline", "--student-fusion", "minimal"]
     r = subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

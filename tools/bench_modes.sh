@@ -2,7 +2,7 @@
 # Dev tool: bench.py under the three streaming-GEMM modes (selective default / off / all), one line each.
 out=gpurun_out/${1:-modes}; mkdir -p $out
 for m in all 1 0; do
-  KD_GEMM_STREAM=$m python bench.py --steps ${2:-10} --warmup 3 --no-cpu-baseline $([ $m != all ] && echo --no-selfcheck) > $out/bench_$m.json 2> $out/bench_$m.err
+  KD_GEMM_STREAM=$m python bench.py --steps ${2:-10} --warmup 3 --full --no-cpu-baseline $([ $m != all ] && echo --no-selfcheck) > $out/bench_$m.json 2> $out/bench_$m.err
   python - <<PY
 import json
 d = json.load(open("$out/bench_$m.json"))

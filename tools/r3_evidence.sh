@@ -15,7 +15,7 @@ step pmc2 400 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES -
 step pmc3 400 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --output-format csv -d $O/pmc3 -o p -- $B
 step pmc4 400 rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $O/pmc4 -o p -- $B
 step dw256 300 ./tools/bench_dw 256
-step bench 900 python bench.py --steps 10 --warmup 3 --dump-launches $O/launches.txt
+step bench 900 python bench.py --steps 10 --warmup 3 --full --dump-launches $O/launches.txt
 BF="python3 tools/bf16_forward_only.py"
 step bf16stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bf16stats -o p -- $BF
 step bf16F 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/bf16F -o p -- $BF

@@ -11,5 +11,5 @@ B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-selfcheck --no-b
 step pmcF 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmcF -o p -- $B
 step pmcW 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmcW -o p -- $B
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-step bench 900 python bench.py
+step bench 900 python bench.py --full
 tail -n 5 $O/tests.log; tail -n 2 $O/smoke.log; tail -n 1 $O/bench.log | cut -c1-200

@@ -2,7 +2,7 @@
 # usage: r3_prof.sh <tag>: kernel-trace + stats of the default bench workload -> gpurun_out/<tag>/
 O=gpurun_out/$1; mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-selfcheck --no-bf16-forward --no-side-benches > $O/stats_bench.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-selfcheck --no-bf16-forward --no-side-benches > $O/stats_bench.log 2>&1
 grep '^{' $O/stats_bench.log | tail -1 > $O/stats_bench.json
 ls $O/stats | head
 ls $O/stats/*/p_kernel_trace.csv >/dev/null 2>&1 || { mkdir -p $O/stats/x; mv $O/stats/p_*.csv $O/stats/x/; }
