@@ -13,7 +13,6 @@
 // argmax agreement with the fp32 path -- this mode is NOT part of the fp32 parity contract.
 #include "kd_common.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -318,18 +317,11 @@ __device__ __forceinline__ float xor1(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
 }
 
-#ifndef KD_BF16_PROBE
-#define KD_BF16_PROBE 0   // dev builds only: timing probes, results WRONG by construction (1: no C stores, 2: no A loads)
-#endif
-#ifndef KD_BF16_OCC
-#define KD_BF16_OCC 2
-#endif
-#ifndef KD_BF16_CH
-#define KD_BF16_CH 8
-#endif
+constexpr int BF16_OCC = 2;           // first form: workgroups per CU (launch bounds and grid cap)
+constexpr int BF16_CH = 8;            // first form: k-steps (of 16) per register chunk
 template <int NB, int AIN, int EPI>
-__global__ __launch_bounds__(64 * BW, KD_BF16_OCC) void pw_gemm_bf16_kernel(GemmBfArgs g) {
-  constexpr int N = 32 * NB, CH = KD_BF16_CH;                         // CH: k-steps (of 16) per register chunk
+__global__ __launch_bounds__(64 * BW, BF16_OCC) void pw_gemm_bf16_kernel(GemmBfArgs g) {
+  constexpr int N = 32 * NB, CH = BF16_CH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   bf16_t* Wh = reinterpret_cast<bf16_t*>(smem_raw);                   // [N][K] bf16, 16-byte chunks swizzled
   float* Co = reinterpret_cast<float*>(smem_raw + (size_t)N * g.K * 2);  // AIN 3: [7][K]
@@ -372,9 +364,6 @@ __global__ __launch_bounds__(64 * BW, KD_BF16_OCC) void pw_gemm_bf16_kernel(Gemm
   // A fragment of k-step u for this lane: 8 consecutive k of row r starting at 16 u + 8 h
   auto load_frag = [&](int64_t gm, int u) -> u32x4 {
     if (AIN == 0) {
-#if KD_BF16_PROBE & 2
-      return u32x4{(uint32_t)gm, (uint32_t)u, 0x3f803f80u, 0x3f803f80u};
-#endif
       return ld16(reinterpret_cast<const bf16_t*>(g.A) + gm * g.lda + 16 * u + 8 * h);
     } else if (AIN == 1) {
       const float* p = reinterpret_cast<const float*>(g.A) + gm * g.lda + 16 * u + 8 * h;
@@ -450,11 +439,7 @@ __global__ __launch_bounds__(64 * BW, KD_BF16_OCC) void pw_gemm_bf16_kernel(Gemm
           float lo = odd ? x1 : v0, hi = odd ? v1 : x0;
           const int64_t row = m0 + rbase + 4 * h + (odd ? 1 : 0);
           const int col = n0 + 32 * j + (r & ~1);
-#if KD_BF16_PROBE & 1
-          if (row < M && lo == 123456.75f) {
-#else
           if (row < M) {
-#endif
             if (g.res) {
               const uint32_t rr = *reinterpret_cast<const uint32_t*>(g.res + row * g.ldres + col);
               lo += bf_lo(rr); hi += bf_hi(rr);
@@ -494,7 +479,7 @@ __global__ __launch_bounds__(64 * BW, KD_BF16_OCC) void pw_gemm_bf16_kernel(Gemm
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Round 4: second form of the same GEMM for the common case (A bf16, C bf16: AIN 0 / EPI 0), written after timing probes of the first
-// (tools/r4_probe_bf16.sh, -DKD_BF16_PROBE): over the 18 launches of a forward 3.59 ms, 2.03 ms without the C stores (and the residual
+// (timing-only builds without the C stores / without the A loads): over the 18 launches of a forward 3.59 ms, 2.03 ms without the C stores (and the residual
 // loads inside their guards), 2.56 ms without the A loads -- the layers with many output columns ran at 2.9-3.0 TB/s, the residual
 // layers (32 -> 32 at 4.2 M rows: 371 us, 86 without its epilogue) waited for one residual dword after the other, and the K = 32 / 64
 // layers had 2-4 KB per wave in flight.  What changed:
@@ -509,7 +494,7 @@ __global__ __launch_bounds__(64 * BW, KD_BF16_OCC) void pw_gemm_bf16_kernel(Gemm
 //     instead of 16 (the fp32 streaming kernels' transposition tile, kd_gemm_stream_kernel.h);
 //   * full units run without predicates; the one partial unit of a launch is handled after the loop by the wave it falls to.
 // Same products, same fp32 accumulation order per output element, same single rounding: the same bits as the first form
-// (tests/test_gpu_bf16.py compares the two).  KD_BF16_V2=0 keeps the first form everywhere.
+// (tests/test_gpu_bf16.py compares the two; a device-side row count selects the first form).
 template <int NB, int KU, bool RES>
 __global__ __launch_bounds__(64 * BW, 2) void pw_gemm_bf16_v2_kernel(GemmBfArgs g) {
   constexpr int N = 32 * NB, K = 16 * KU, CPR = K / 8;
@@ -774,7 +759,7 @@ template <int NB>
 int launch_gemm_bf16(GemmBfArgs& g, int ain, int epi, hipStream_t st) {
   const int ntiles = g.N / (32 * NB);
   int64_t want = (g.M + 32 * BW - 1) / (32 * BW);
-  int cap = 128 * KD_BF16_OCC / ntiles; if (cap < 1) cap = 1;
+  int cap = 128 * BF16_OCC / ntiles; if (cap < 1) cap = 1;
   const dim3 grid((unsigned)(want < cap ? want : cap), ntiles);
   const size_t lds = (size_t)32 * NB * g.K * 2 + (ain == 3 ? (size_t)7 * g.K * 4 : 0);
 #define KD_BCASE(A_, E_)                                                                                               \
@@ -800,7 +785,8 @@ int launch_gemm_bf16_v2_nk(GemmBfArgs& g, hipStream_t st) {
   const dim3 grid((unsigned)(want < cap ? want : cap), ntiles);
   const size_t lds = (size_t)32 * NB * 16 * KU * 2 + (size_t)BW * 32 * (64 * TWB + 16);
   const void* fn = g.res ? (const void*)pw_gemm_bf16_v2_kernel<NB, KU, true> : (const void*)pw_gemm_bf16_v2_kernel<NB, KU, false>;
-  const hipError_t le = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  static std::atomic<uint64_t> lds_raised[2];                       // per instance: lds is a compile-time function of <NB, KU, RES>
+  const hipError_t le = kd_raise_dynamic_lds(fn, lds, lds_raised[g.res ? 1 : 0]);
   KD_REQUIRE(le == hipSuccess, (int)le, "kd_bf16_pwconv: cannot raise the dynamic LDS limit to %zu B: %s", lds, hipGetErrorString(le));
   if (g.res) hipLaunchKernelGGL((pw_gemm_bf16_v2_kernel<NB, KU, true>), grid, dim3(64 * BW), lds, st, g);
   else hipLaunchKernelGGL((pw_gemm_bf16_v2_kernel<NB, KU, false>), grid, dim3(64 * BW), lds, st, g);
@@ -822,8 +808,7 @@ int launch_gemm_bf16_v2_n(GemmBfArgs& g, hipStream_t st) {
 }
 // the second form where it has an instance: K in {32, 64, 128, 192, 256, 384, 512, 768}, 16-byte-aligned rows of C, fewer than 2^31 rows
 int launch_gemm_bf16_v2(GemmBfArgs& g, hipStream_t st) {
-  static const int on = [] { const char* e = getenv("KD_BF16_V2"); return e ? atoi(e) : 1; }();
-  if (!on || g.K % 16 != 0 || g.M >= ((int64_t)1 << 31) || g.ldc % 8 != 0 || !kd_aligned16(g.C) || g.lda * 128 >= ((int64_t)1 << 31) ||
+  if (g.K % 16 != 0 || g.M >= ((int64_t)1 << 31) || g.ldc % 8 != 0 || !kd_aligned16(g.C) || g.lda * 128 >= ((int64_t)1 << 31) ||
       g.ldc * 32 >= ((int64_t)1 << 31) || (g.res && g.ldres * 32 >= ((int64_t)1 << 31)))
     return KD_BF16_V2_NO_INSTANCE;
   const int SL = g.K >= 128 ? 1 : 128 / g.K;
@@ -866,12 +851,11 @@ int kd_bf16_dwconv3x3(const void* x, const float* w, const float* sc, const floa
   int groups, slots;
   const int grid = cg8_layout((int64_t)B * ((Ho + DWB_SEG - 1) / DWB_SEG) * Wo, C, groups, slots);
   DwBfArgs a{(const bf16_t*)x, w, sc, sh, act, (bf16_t*)y, B, H, W, C, Ho, Wo, stride, groups, slots};
-  static const int pipe = [] { const char* e = getenv("KD_BF16_DW_PIPE"); return e ? atoi(e) : 1; }();
-  if (stride == 1 && pipe && Ho % 16 == 0) {
+  if (stride == 1 && Ho % 16 == 0) {
     const int g16 = cg8_layout((int64_t)B * (Ho / 16) * Wo, C, groups, slots);
     a.groups = groups; a.slots = slots;
     hipLaunchKernelGGL(dw_bf16_s1_pipe_kernel<16>, dim3(g16), dim3(256), 0, (hipStream_t)stream, a);
-  } else if (stride == 1 && pipe && Ho % 8 == 0) {
+  } else if (stride == 1 && Ho % 8 == 0) {
     const int g8 = cg8_layout((int64_t)B * (Ho / 8) * Wo, C, groups, slots);
     a.groups = groups; a.slots = slots;
     hipLaunchKernelGGL(dw_bf16_s1_pipe_kernel<8>, dim3(g8), dim3(256), 0, (hipStream_t)stream, a);

@@ -311,10 +311,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(BwdReduceArgs a) {
   }
 }
 
-// the four-channel form where the slab is tall enough for it to pay (KD_BN_TALL=0: never -- the A/B switch of tools/)
+// the four-channel form where the slab is tall enough for it to pay
+constexpr int BN_TALL_ROWS = 1024;
 bool slab_is_tall(const float* partial, int rows, int C, int pstride) {
-  static const int min_rows = [] { const char* e = getenv("KD_BN_TALL"); return e ? atoi(e) : 1024; }();
-  return min_rows > 0 && rows >= min_rows && C % 4 == 0 && pstride % 4 == 0 && kd_aligned16(partial);
+  return rows >= BN_TALL_ROWS && C % 4 == 0 && pstride % 4 == 0 && kd_aligned16(partial);
 }
 
 }  // namespace

@@ -126,7 +126,7 @@ __device__ __forceinline__ float kd_wave_sum(float v) {
 }
 
 // out[i] = sum_s slab[s][i], s in fixed order (deterministic); defined in kd_runtime.hip
-int kd_nt_store(size_t bytes);       // 1: a tensor of this size should be stored with the non-temporal hint (KD_NT_STORE=0 disables)
+int kd_nt_store(size_t bytes);       // 1: a tensor of this size (>= 64 MiB) should be stored with the non-temporal hint
 int kd_slab_reduce_launch(const float* slab, int nsplit, int64_t n, float* out, hipStream_t st);
 int kd_slab_reduce_tall_launch(float* slab, int rows, int64_t n, float* out, hipStream_t st);   // clobbers the slab
 

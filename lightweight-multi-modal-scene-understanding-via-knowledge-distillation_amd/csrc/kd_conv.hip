@@ -7,7 +7,6 @@
 #include <type_traits>
 
 #include <atomic>
-#include <cstdlib>
 
 namespace {
 
@@ -79,10 +78,6 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
 // constants-offset reads of `w` -- scalar loads into SGPRs (s_load_dwordx*), no LDS and no per-fma ds_read; BatchNorm sums are
 // kept per thread in registers over all of the thread's pixels and reduced once at the end of the kernel (the first form
 // staged every 256-pixel batch through LDS and let 64 threads add 256 values each).
-// timing-only probes of dev builds (-DKD_STEM_PROBE=bits; results WRONG by construction): 1 no stores, 2 no input loads, 4 a quarter of the channels
-#ifndef KD_STEM_PROBE
-#define KD_STEM_PROBE 0
-#endif
 // FIN (round 4, inference: eval mode without autograd -- the frozen KD teacher, validation): the stem's BatchNorm + activation
 // finish, act(fma(raw, sc[c], sh[c])), applied here instead of by a kd_bn_act_apply pass over the [B, 32, H/2, W/2] map (the same
 // operations in the same order: identical bits; 0.23 ms per step at 256 frames).  sc / sh are wave-uniform scalar loads.
@@ -122,13 +117,13 @@ __global__ __launch_bounds__(256) void stem_fwd2_kernel(const float* __restrict_
           for (int kw = 0; kw < 3; ++kw) {
             const int wi = 2 * wo - 1 + kw;
             const bool ok = hi >= 0 && hi < H && wi >= 0 && wi < W;
-            const float t = (KD_STEM_PROBE & 2) ? (float)(hi + wi) : xp[(int64_t)(ok ? hi : 0) * W + (ok ? wi : 0)];
+            const float t = xp[(int64_t)(ok ? hi : 0) * W + (ok ? wi : 0)];
             v[ci * 9 + kh * 3 + kw] = ok ? t : 0.f;
           }
         }
       }
 #pragma unroll
-      for (int c4 = 0; c4 < ((KD_STEM_PROBE & 4) ? 8 : 32); c4 += 4) {
+      for (int c4 = 0; c4 < 32; c4 += 4) {
         float a[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(256) void stem_fwd2_kernel(const float* __restrict_
     for (int k = 0; k < 8; ++k) {
       const int pix = 8 * k + (lane >> 3), col = (lane & 7) * 4;
       const float4 o = kd_ld4(tile + pix * TLD + col);
-      if (!(KD_STEM_PROBE & 1) && wbase + pix < npix) kd_st4(y + (wbase + pix) * 32 + col, o);
+      if (wbase + pix < npix) kd_st4(y + (wbase + pix) * 32 + col, o);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -1177,17 +1172,9 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_sw_kernel(DwBwdArgs a) {
 }  // namespace
 
 // stride-1 backward form: 0 separate data / weight kernels, 1 fused column walk, 2 fused tile form, 3 (default) by shape
-// (dw_fused_form below: the measurements behind the choice).  KD_DW_FUSED / kd_set_dw_bwd_mode.
-static std::atomic<int> g_dw_mode{-1};
-static int kd_dw_fused_mode() {
-  int m = g_dw_mode.load(std::memory_order_relaxed);
-  if (m < 0) {
-    const char* e = getenv("KD_DW_FUSED");
-    m = (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 3;
-    g_dw_mode.store(m, std::memory_order_relaxed);
-  }
-  return m;
-}
+// (dw_fused_form below: the measurements behind the choice).  kd_set_dw_bwd_mode.
+static std::atomic<int> g_dw_mode{3};
+static int kd_dw_fused_mode() { return g_dw_mode.load(std::memory_order_relaxed); }
 
 // Thread layout of the column-walk kernels.  A block is 256 threads = `slots` adjacent image columns x `groups` channel quads
 // (float4 lanes).  Up to 64 quads one block spans all channels; wider tensors (C = 384 / 768: 96 / 192 quads left room for
@@ -1226,8 +1213,7 @@ int kd_stem_conv_fwd(const float* x_nchw, const float* w, float* y_nhwc, float* 
   const int64_t npix = (int64_t)B * Ho * Wo;
   const int grid = (int)kd_stem_stat_rows(npix);
   hipStream_t st = (hipStream_t)stream;
-  static const bool old_form = getenv("KD_STEM_FORM") && atoi(getenv("KD_STEM_FORM")) == 1;      // A/B: the LDS-weights form of rounds 1-2
-  if (Cin == 3 && !old_form) {
+  if (Cin == 3) {
     if (partial) hipLaunchKernelGGL((stem_fwd2_kernel<3, true>), dim3(grid), dim3(256), 0, st, x_nchw, w, y_nhwc, partial, B, H, W, Ho, Wo);
     else hipLaunchKernelGGL((stem_fwd2_kernel<3, false>), dim3(grid), dim3(256), 0, st, x_nchw, w, y_nhwc, partial, B, H, W, Ho, Wo);
     return kd_check_launch("kd_stem_conv_fwd");
@@ -1276,11 +1262,10 @@ int kd_dwconv3x3_fwd(const float* x, const float* sc, const float* sh, int act, 
   const DwLayout l = dw_layout((int64_t)B * Ho * Wo, C);
   DwArgs a{x, sc, sh, act, w, y, partial, B, H, W, C, Ho, Wo, stride, l.groups, l.slots, l.nchunk,
            kd_nt_store((size_t)B * Ho * Wo * C * sizeof(float))};
-  static const int pipe = [] { const char* e = getenv("KD_DW_FWD_PIPE"); return e ? atoi(e) : 3; }();     // bit 0: stride 1, bit 1: stride 2
   const bool small = (int64_t)B * H * W * C < ((int64_t)1 << 31);      // the pipelined kernel addresses x by 32-bit element offsets
-  if (stride == 1 && (pipe & 1) && small && Ho % 16 == 0) hipLaunchKernelGGL((dw_fwd_pipe_kernel<1, 16>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
-  else if (stride == 1 && (pipe & 1) && small && Ho % 8 == 0) hipLaunchKernelGGL((dw_fwd_pipe_kernel<1, 8>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
-  else if (stride == 2 && (pipe & 2) && small && Ho % 8 == 0) hipLaunchKernelGGL((dw_fwd_pipe_kernel<2, 8>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  if (stride == 1 && small && Ho % 16 == 0) hipLaunchKernelGGL((dw_fwd_pipe_kernel<1, 16>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  else if (stride == 1 && small && Ho % 8 == 0) hipLaunchKernelGGL((dw_fwd_pipe_kernel<1, 8>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  else if (stride == 2 && small && Ho % 8 == 0) hipLaunchKernelGGL((dw_fwd_pipe_kernel<2, 8>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
   else if (stride == 1) hipLaunchKernelGGL(dw_fwd_sw_kernel<1>, dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(dw_fwd_sw_kernel<2>, dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
   return kd_check_launch("kd_dwconv3x3_fwd");
@@ -1391,6 +1376,6 @@ int kd_dwconv3x3_bwd_add(const float* D, const float* Y, const float* al, const 
 int64_t kd_dwconv_bwd_stat_rows(int64_t npix_in, int C) { return dw_layout(npix_in, C).rows; }
 
 // 0 separate kernels, 1 fused column walk, 2 fused tile form, 3 choose by shape (default); returns the previous mode
-int kd_set_dw_bwd_mode(int mode) { (void)kd_dw_fused_mode(); return g_dw_mode.exchange(mode < 0 ? 0 : (mode > 3 ? 3 : mode)); }
+int kd_set_dw_bwd_mode(int mode) { return g_dw_mode.exchange(mode < 0 ? 0 : (mode > 3 ? 3 : mode)); }
 
 }  // extern "C"

@@ -18,22 +18,6 @@ namespace {
 
 std::atomic<int> g_gemm_split{0};
 
-// Dev build only (-DKD_DBG_PHASES [-DKD_DBG_EPI]): per-phase clock64() totals of wave 0 of every workgroup, read back by
-// tools/bench_gemm through kd_dbg_read -- how the epilogue store drains and the per-K-tile serialisation were found.
-#ifdef KD_DBG_PHASES
-__device__ unsigned long long kd_dbg_counters[8];
-#define KD_STAMP(i) do { const long long t_ = clock64(); ph_acc[i] += t_ - ph_t; ph_t = t_; } while (0)
-#ifdef KD_DBG_EPI          // bins: 0 barrier | 1 MFMA tail + staging writes | 2 barrier | 3 row loop half 0 | 4 everything before the epilogue | 5 row loop half 1 + stats
-#define KD_PH(i) KD_STAMP(((i) == 5) ? 5 : 4)
-#define KD_PHE(i) KD_STAMP(i)
-#else
-#define KD_PH(i) KD_STAMP(i)
-#define KD_PHE(i) do {} while (0)
-#endif
-#else
-#define KD_PH(i) do {} while (0)
-#define KD_PHE(i) do {} while (0)
-#endif
 
 
 constexpr int BM = 128, BK = 32, LDSLD = 36;   // BM: slab-row granularity; 36-float LDS rows: ds_read_b128 conflict-free
@@ -206,14 +190,9 @@ __global__ __launch_bounds__(256, SPLIT ? ((WM == 2 && PRO != 2 && PRO != 3 && P
     }
   };
 
-#ifdef KD_DBG_PHASES
-  long long ph_t = clock64(), ph_acc[6] = {0, 0, 0, 0, 0, 0};
-#endif
   auto k_tile = [&](int kt, float4 (&ra)[AF], float4 (&rb)[BF], float4 (&co)[NCO]) {
     transform(kt, ra, rb, co);
-    KD_PH(0);                          // wait for the tile's loads + BN/act transform
     kd_lds_barrier();
-    KD_PH(1);                          // barrier: previous MFMA phase of the slowest wave
     if (SPLIT) {
 #pragma unroll
       for (int i = 0; i < AF; ++i) {
@@ -241,9 +220,7 @@ __global__ __launch_bounds__(256, SPLIT ? ((WM == 2 && PRO != 2 && PRO != 3 && P
 #pragma unroll
       for (int i = 0; i < BF; ++i) kd_st4(Bs + ((tid >> 3) + 32 * i) * LDSLD + c4 * 4, rb[i]);
     }
-    KD_PH(2);                          // split + LDS stores
     kd_lds_barrier();
-    KD_PH(3);                          // barrier after the LDS image
     if (kt + (PF2 ? 2 : 1) < nk) issue_loads(kt + (PF2 ? 2 : 1), ra, rb, co);  // the freed stage refills under this tile's MFMAs
     if (SPLIT) {
 #pragma unroll
@@ -296,7 +273,6 @@ __global__ __launch_bounds__(256, SPLIT ? ((WM == 2 && PRO != 2 && PRO != 3 && P
   } else {
     for (int kt = 0; kt < nk; ++kt) k_tile(kt, ra0, rb0, co0);
   }
-  KD_PH(4);                            // MFMA phases (incl. issuing the prefetch)
 
   // ---- EPI4: eval BatchNorm + ReLU + BEV scatter-max straight from the accumulator tile -----------------------
   // (frozen teacher / validation: the [points, C] output of the last point-MLP layer is never written).  X = int
@@ -408,17 +384,13 @@ __global__ __launch_bounds__(256, SPLIT ? ((WM == 2 && PRO != 2 && PRO != 3 && P
   constexpr int NI = (WM * 32) / RG;                   // rows per thread per half
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    KD_PHE(h == 0 ? 4 : 3);
     kd_lds_barrier();                                 // LDS free: K-loop reads / previous half done
-    KD_PHE(0);
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         T[(wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * TLD + wc * 64 + ni * 32 + (lane & 31)] = acc[h][ni][r];
-    KD_PHE(1);
     kd_lds_barrier();
-    KD_PHE(2);
     // All global LOADS of this half are issued before its first store (clamped addresses, no branches), so no
     // wait on a load ever has an older store in front of it in the in-order vmcnt queue.
     float4 xr[(EPI_BWD || EPI == 5) ? NI : 1];
@@ -535,13 +507,6 @@ __global__ __launch_bounds__(256, SPLIT ? ((WM == 2 && PRO != 2 && PRO != 3 && P
       }
     }
   }
-  KD_PH(5);                            // epilogue
-#ifdef KD_DBG_PHASES
-  if (tid == 0) {
-    atomicAdd(&kd_dbg_counters[6], 1ull);
-    for (int i = 0; i < 6; ++i) atomicAdd(&kd_dbg_counters[i], (unsigned long long)ph_acc[i]);
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -549,11 +514,6 @@ __global__ __launch_bounds__(256, SPLIT ? ((WM == 2 && PRO != 2 && PRO != 3 && P
 // the rows of each staged chunk; the grid additionally splits M into `nsplit` slices whose partial
 // tiles go to a slab [nsplit][N][K] summed in fixed order by wgrad_reduce_kernel (deterministic).
 // (WgradArgs and kd_tr_frag: kd_gemm_args.h -- shared with the role-specialised form in kd_wgrad_rs.hip)
-// timing-only probes of dev builds (-DKD_WG_PROBE=bits; results WRONG by construction): 1 one of the six piece products, 2 every chunk
-// loads the slice's FIRST rows (operands stay cache-resident: no HBM latency)
-#ifndef KD_WG_PROBE
-#define KD_WG_PROBE 0
-#endif
 template <int WN, int WK, int WM, int DMODE, int AMODE, bool SPLIT>
 __global__ __launch_bounds__(256, SPLIT ? 2 : 1) void pw_wgrad_kernel(WgradArgs g) {
   constexpr int KS = WM == 1 ? 2 : 1;                           // SPLIT: 16-row MFMA steps per wave per chunk
@@ -626,7 +586,6 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 1) void pw_wgrad_kernel(WgradArgs 
     }
   };
   auto load_chunk = [&](int64_t mc) {
-    if (KD_WG_PROBE & 2) mc = mbeg;
     if constexpr (DMODE == 3) {
       // the table rows of THIS chunk were fetched one chunk ago (tr_nxt): no dependent load in the steady state
 #pragma unroll
@@ -737,7 +696,7 @@ __global__ __launch_bounds__(256, SPLIT ? 2 : 1) void pw_wgrad_kernel(WgradArgs 
           }
         constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
 #pragma unroll
-        for (int t = 0; t < ((KD_WG_PROBE & 1) ? 1 : 6); ++t)
+        for (int t = 0; t < 6; ++t)
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -835,10 +794,9 @@ int launch_wgrad(WgradArgs& g, size_t ws_bytes, float* dW, hipStream_t st) {
   g.rows_per_split = (int)(cps * CH);
   nsplit = (int)((g.M + g.rows_per_split - 1) / g.rows_per_split);
   const dim3 grid(ntiles * nsplit), blk(256);
-  // measured on the same box (tools/bench_wgrad.py, 256 frames, KD_WGRAD_XCD=0|1): the XCD-aware order wins 1-8 % where a row slice has
+  // measured on the same box (tools/bench_wgrad.py, 256 frames, both orders forced): the XCD-aware order wins 1-8 % where a row slice has
   // three output tiles (64 <-> 384 layers) and LOSES 29-34 % where it has six (128 <-> 768: 462 -> 598 us), so it is chosen by tile count
-  static const int xcd_env = [] { const char* e = getenv("KD_WGRAD_XCD"); return e ? atoi(e) : -1; }();
-  g.xcd_order = xcd_env >= 0 ? xcd_env : (ntiles > 1 && ntiles <= 3);
+  g.xcd_order = ntiles > 1 && ntiles <= 3;
   if (g.d_mode == 3) hipLaunchKernelGGL((pw_wgrad_kernel<WN, WK, WM, 3, 1, SPLIT>), grid, blk, 0, st, g);
   else if (g.d_mode == 2 && g.a_mode == 2) hipLaunchKernelGGL((pw_wgrad_kernel<WN, WK, WM, 2, 2, SPLIT>), grid, blk, 0, st, g);
   else if (g.d_mode == 2 && g.a_mode == 1) hipLaunchKernelGGL((pw_wgrad_kernel<WN, WK, WM, 2, 1, SPLIT>), grid, blk, 0, st, g);
@@ -935,14 +893,6 @@ extern "C" {
 // 0: v_mfma_f32_32x32x2_f32 (exact fp32 products); 1: bf16x6 split products on v_mfma_f32_32x32x16_bf16.
 // Process-wide switch for the forward / dgrad / wgrad GEMMs; returns the previous value.
 int kd_set_gemm_split(int on) { return g_gemm_split.exchange(on ? 1 : 0); }
-#ifdef KD_DBG_PHASES
-int kd_dbg_read(unsigned long long* out, int reset) {
-  hipDeviceSynchronize();
-  hipMemcpyFromSymbol(out, HIP_SYMBOL(kd_dbg_counters), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(kd_dbg_counters), z, sizeof(z)); }
-  return 0;
-}
-#endif
 
 // Rows of the BN-statistics slab a GEMM over M rows writes ([rows][2][N] floats).
 int64_t kd_pwconv_stat_rows(int64_t M) { return (M + BM - 1) / BM; }

@@ -3,11 +3,6 @@
 #include "kd_gemm_stream_kernel.h"
 
 #include <atomic>
-#include <cstdlib>
-
-#ifdef KD_STREAM_DBG
-namespace kd_stream { __device__ unsigned long long kd_stream_dbg[8]; }
-#endif
 
 using namespace kd_stream;
 
@@ -17,17 +12,10 @@ int kd_stream_bwd2_dispatch(const GemmArgs& g, int kb, int nb, int pro, int epi,
 
 namespace {
 
-std::atomic<int> g_stream_on{-1};
+// 0 off, 1 only the forward shapes that win in isolation, 2 every covered shape (default), 3 forward shapes only
+std::atomic<int> g_stream_on{2};
 
-int stream_mode() {          // 0 off, 1 only the forward shapes that win in isolation, 2 every covered shape (default)
-  int v = g_stream_on.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("KD_GEMM_STREAM");
-    v = (e && e[0] == '0') ? 0 : ((e && e[0] == '1') ? 1 : ((e && e[0] == '3') ? 3 : 2));
-    g_stream_on.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
+int stream_mode() { return g_stream_on.load(std::memory_order_relaxed); }
 
 struct StreamCfg { int kb, nb, ntiles; };
 
@@ -131,11 +119,3 @@ int kd_gemm_stream_launch(GemmArgs& g, int pro, int epi, hipStream_t st) {
 }
 
 extern "C" int kd_set_gemm_stream(int mode) { return g_stream_on.exchange(mode < 0 ? 0 : (mode > 3 ? 2 : mode)); }   // 0 off, 1 selective, 2 all, 3 forward only; returns the previous mode
-#ifdef KD_STREAM_DBG
-extern "C" int kd_stream_dbg_read(unsigned long long* out, int reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(kd_stream::kd_stream_dbg), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(kd_stream::kd_stream_dbg), z, sizeof(z)); }
-  return 0;
-}
-#endif

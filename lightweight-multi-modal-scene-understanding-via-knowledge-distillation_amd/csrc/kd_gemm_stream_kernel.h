@@ -45,15 +45,6 @@ namespace kd_stream {
 typedef __attribute__((ext_vector_type(4))) float f4v;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-// Dev build only (-DKD_STREAM_DBG): per-phase s_memtime totals over all waves, read back by tools/bench_stream through
-// kd_stream_dbg_read: [0] load wait + first conversion, [1] k-loop, [2] next loads + epilogue, [3] units, [4] s_memrealtime
-#ifdef KD_STREAM_DBG
-extern __device__ unsigned long long kd_stream_dbg[8];
-#define KD_SSTAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); dbg_acc[i] += t_ - dbg_t; dbg_t = t_; } while (0)
-#else
-#define KD_SSTAMP(i) do {} while (0)
-#endif
-
 constexpr int SW = 8;                 // waves per workgroup: two per SIMD share the resident W planes
 
 // 16-byte chunk swizzle of a W row of CPR chunks (CPR = K / 8): the 16 lanes of a ds_read_b128 group read the same
@@ -66,26 +57,22 @@ __device__ __forceinline__ int sw_key(int n) {
   else { static_assert(CPR == 4, "K must be 32 or a multiple of 64"); return (n >> 2) & 3; }
 }
 
-// KD_STREAM_TSTORE (default 1): a finished 32 x 32 accumulator block leaves through a wave-private LDS tile (rows padded to 36 floats;
+// Transposed store: a finished 32 x 32 accumulator block leaves through a wave-private LDS tile (rows padded to 36 floats;
 // LDS is in-order per wave: no barrier) as four 16-byte-per-lane stores of eight whole 128-byte row segments each, instead of
-// sixteen dword stores (two 128-byte segments each).  =0 builds the dword form (A/B: profiles/r04_stream_tstore_ab.txt).
-#ifndef KD_STREAM_TSTORE
-#define KD_STREAM_TSTORE 1
-#endif
-constexpr bool STREAM_TSTORE = KD_STREAM_TSTORE != 0;
-// Which instances use it, from the in-step per-launch A/B (same box, tools/r4_ab_stream.sh, profiles/r04_stream_tstore_ab.txt): the
+// sixteen dword stores (two 128-byte segments each).
+// Which instances use it, from the in-step per-launch A/B (same box, profiles/r04_stream_tstore_ab.txt): the
 // 128-wide column tiles gain 2-6 % (128 -> 128: 236 -> 224 us, LiDAR layer 2: 4581 -> 4428 us) and so do the 32 -> 192 expand launches
 // (three 64-wide tiles: 787 -> 748 us); the narrow outputs (N = 32 / 64 in one tile) and the layer-0-recompute launch lose 2-8 %
 // (their dword stores already write whole 128-byte segments; the transposition only adds LDS traffic); the mask epilogue (EPI 2)
 // sits at the 256-register limit and spills with the tile.
 constexpr bool stream_tstore(int kb, int nb, int pro, int epi) {
-  return STREAM_TSTORE && epi != 2 && pro != 3 && (nb == 4 || (nb == 2 && kb == 1));
+  return epi != 2 && pro != 3 && (nb == 4 || (nb == 2 && kb == 1));
 }
 constexpr int STREAM_TR = 32 * 36;                                      // floats per wave-private transposition tile
 
 constexpr int stream_nco(int pro) { return pro == 1 ? 2 : (pro == 3 ? 7 : ((pro == 2 || pro == 4) ? 5 : 0)); }
 constexpr size_t stream_lds_bytes(int K, int N, int pro) {
-  return (size_t)3 * N * K * 2 + (size_t)(stream_nco(pro) > 0 ? stream_nco(pro) : 1) * K * 4 + (STREAM_TSTORE ? (size_t)8 * STREAM_TR * 4 : 0);
+  return (size_t)3 * N * K * 2 + (size_t)(stream_nco(pro) > 0 ? stream_nco(pro) : 1) * K * 4 + (size_t)8 * STREAM_TR * 4;
 }
 
 // KB = K / 32, KC = chunk width / 32 (divides KB), NB = column-tile width / 32.
@@ -103,7 +90,7 @@ __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned short* Wh = reinterpret_cast<unsigned short*>(smem_raw);      // [3][N][K] bf16, swizzled
   float* Co = reinterpret_cast<float*>(smem_raw + 3 * WPL * 2);         // [NCO][K] coefficient tables
-  float* trt = Co + (NCO > 0 ? NCO : 1) * K + (threadIdx.x >> 6) * STREAM_TR;   // this wave's transposition tile (STREAM_TSTORE)
+  float* trt = Co + (NCO > 0 ? NCO : 1) * K + (threadIdx.x >> 6) * STREAM_TR;   // this wave's transposition tile (stream_tstore)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int n0 = blockIdx.y * N;                                         // column tile (N_total > N: several tiles)
@@ -374,10 +361,6 @@ __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
     load_unit(s, 0, rc[0]);
     load_b(Wh, 0, 0, b_cur);
   }
-#ifdef KD_STREAM_DBG
-  unsigned long long dbg_acc[4] = {0, 0, 0, 0}, dbg_t = __builtin_amdgcn_s_memtime();
-  const unsigned long long dbg_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
   for (; s < nslab; s += wtot) {
     f32x16 acc[NB];
 #pragma unroll
@@ -399,27 +382,14 @@ __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
         else if (more) load_unit(s + wtot, 0, rc[0]);
       }
       conv_all(rc[DB ? (c & 1) : 0], Cq, c * NUC, a_cur);
-      KD_SSTAMP(0);
       compute_chunk(rc[DB ? (c & 1) : 0], c, a_cur, b_cur, acc);
-      KD_SSTAMP(1);
       if constexpr (!DB) {
         if (c < NCH - 1) load_unit(s, c + 1, rc[0]);
         else if (more) load_unit(s + wtot, 0, rc[0]);
       }
     }
     if (s * 32 + 32 <= M) store_slab(s, acc, std::true_type{}); else store_slab(s, acc, std::false_type{});
-    KD_SSTAMP(2);
-#ifdef KD_STREAM_DBG
-    dbg_acc[3] += 1;
-#endif
   }
-#ifdef KD_STREAM_DBG
-  if (lane == 0) {
-    for (int i = 0; i < 4; ++i) atomicAdd(&kd_stream_dbg[i], dbg_acc[i]);
-    atomicAdd(&kd_stream_dbg[4], __builtin_amdgcn_s_memrealtime() - dbg_r0);
-    atomicAdd(&kd_stream_dbg[5], 1ull);
-  }
-#endif
 
   if (EPI == 1 || EPI_BWD) {
     // one statistics row per WORKGROUP (round 4; one per wave before): the eight waves' column sums meet in LDS -- the weight

@@ -39,24 +39,8 @@ int kd_gemm_split_mode();     // kd_gemm.hip: 1 = bf16x6 split products (default
 
 // Round 4, measured and not kept: the matrix wave that holds a 32 x 32 block of (dy . W2) finishing G1 itself (mask from the vector
 // waves' LDS copy of Y1, BatchNorm sums, sixteen dword stores from the accumulators; no stage tile, no vector-wave epilogue): the L2
-// kernel went from 8.69-8.75 to 9.37-9.47 ms in the step on the same box (tools/r4_ab_lb.sh) -- the sixteen LDS reads, selects and
+// kernel went from 8.69-8.75 to 9.37-9.47 ms in the step on the same box (A/B of the two forms) -- the sixteen LDS reads, selects and
 // stores sit in the matrix waves' issue stream between two chunks' MFMAs, and those waves are not as idle as the vector waves are busy.
-//
-// Dev build only (-DKD_LB_DBG): per-phase s_memtime totals over all waves of a role, read back through kd_lb_dbg_read
-// (tools/bench_lidar_bwd.py): [0..3] role B: dy conversion + LDS stores | load issue | wgrad k-loop | barrier wait;
-// [4..7] role A: dgrad k-loop | epilogue | a1 conversion + load issue | barrier wait; [8] iterations (role A waves)
-#ifdef KD_LB_DBG
-__device__ unsigned long long kd_lb_dbg[16];
-#define KD_LSTAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); dbg_acc[i] += t_ - dbg_t; dbg_t = t_; } while (0)
-#else
-#define KD_LSTAMP(i) do {} while (0)
-#endif
-
-// Timing-only probes of dev builds (-DKD_LB_PROBE=bits; results are WRONG by construction): 1 no G1 stores, 2 no dgrad MFMAs,
-// 4 no wgrad MFMAs, 8 no dy transform (planes of the raw Y2), 16 no epilogue arithmetic, 32 no table gathers
-#ifndef KD_LB_PROBE
-#define KD_LB_PROBE 0
-#endif
 
 namespace {
 
@@ -173,13 +157,6 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
     int trq[2][4];                                                        // table rows of chunk c in trq[c & 1], fetched a full step ahead
     int tvb[2];                                                           // bit i: row i of the chunk lies in a cell (set when its tables are issued)
     float4 s1 = kd_zero4(), s2 = kd_zero4();                              // BatchNorm-1 backward sums of this thread's 4 columns
-    auto split_store = [&](float4 v, unsigned short* d) __attribute__((always_inline)) {
-      uint2 hi, mid, lo;
-      kd_split3(v, hi, mid, lo);
-      *reinterpret_cast<uint2*>(d) = hi;
-      *reinterpret_cast<uint2*>(d + LBPL) = mid;
-      *reinterpret_cast<uint2*>(d + 2 * LBPL) = lo;
-    };
     // one chunk of a dense [M,128] tensor: (wave-uniform chunk base) + (per-lane offset); rows clamped to the chunk's last valid one
     auto load_rows4 = [&](const float* T, int chunk, float4 (&dst)[4]) __attribute__((always_inline)) {
       const float* base = T + (size_t)chunk * (LBCH * LBW);
@@ -203,7 +180,6 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         int t = trw[i];
-        if (KD_LB_PROBE & 32) t = i;
         asm volatile("" : "+v"(t));     // first use of the fetched row HERE: instruction selection otherwise floats the sign tests up
                                         // to the load itself (a full step earlier) and the wait for the fetch with them
         const size_t o = (size_t)(t < 0 ? 0 : t) * LBW + 4 * c4;
@@ -236,7 +212,6 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
           vw[i].y = fmaf(cal.y, a.y == mx.y ? sv.y : 0.f, fmaf(cbe.y, x.y, cga.y));
           vw[i].z = fmaf(cal.z, a.z == mx.z ? sv.z : 0.f, fmaf(cbe.z, x.z, cga.z));
           vw[i].w = fmaf(cal.w, a.w == mx.w ? sv.w : 0.f, fmaf(cbe.w, x.w, cga.w));
-          if (KD_LB_PROBE & 8) vw[i] = x;
         }
         uint2 hi[4], mid[4], lo[4];
         lb_split3_lockstep<4>(vw, hi, mid, lo);
@@ -292,27 +267,22 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
         const float4 d = kd_ld4(stage + bufi * LBXF + xo + 8 * i * LBW), x = kd_ld4(ldx + bufi * LBXF + xo + 8 * i * LBW);
         const bool ok = rb + 8 * i <= last;
         float4 v = make_float4(d.x + zero, d.y + zero, d.z + zero, d.w + zero);
-        if (!(KD_LB_PROBE & 16)) {
-          // v *= relu'(Y1*sc1 + sh1): a select on VCC (no SGPR round trip); rows beyond M count as zero (every tile value is finite:
-          // the fp32 tiles are zero-filled at the start and only ever hold results of finite loads)
-          v.x = kd_affine(x.x, cas.x, cah.x) > 0.f ? v.x : 0.f;
-          v.y = kd_affine(x.y, cas.y, cah.y) > 0.f ? v.y : 0.f;
-          v.z = kd_affine(x.z, cas.z, cah.z) > 0.f ? v.z : 0.f;
-          v.w = kd_affine(x.w, cas.w, cah.w) > 0.f ? v.w : 0.f;
-          const float4 vs = make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
-          s1.x += vs.x; s1.y += vs.y; s1.z += vs.z; s1.w += vs.w;
-          s2.x = fmaf(vs.x, (x.x - cmean.x) * cinv.x, s2.x);
-          s2.y = fmaf(vs.y, (x.y - cmean.y) * cinv.y, s2.y);
-          s2.z = fmaf(vs.z, (x.z - cmean.z) * cinv.z, s2.z);
-          s2.w = fmaf(vs.w, (x.w - cmean.w) * cinv.w, s2.w);
-        } else { s1.x += v.x + x.x; }
-        float* dst = (ok && !(KD_LB_PROBE & 1)) ? cbase + 8 * i * LBW : g.dump + 4 * c4;
+        // v *= relu'(Y1*sc1 + sh1): a select on VCC (no SGPR round trip); rows beyond M count as zero (every tile value is finite:
+        // the fp32 tiles are zero-filled at the start and only ever hold results of finite loads)
+        v.x = kd_affine(x.x, cas.x, cah.x) > 0.f ? v.x : 0.f;
+        v.y = kd_affine(x.y, cas.y, cah.y) > 0.f ? v.y : 0.f;
+        v.z = kd_affine(x.z, cas.z, cah.z) > 0.f ? v.z : 0.f;
+        v.w = kd_affine(x.w, cas.w, cah.w) > 0.f ? v.w : 0.f;
+        const float4 vs = make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
+        s1.x += vs.x; s1.y += vs.y; s1.z += vs.z; s1.w += vs.w;
+        s2.x = fmaf(vs.x, (x.x - cmean.x) * cinv.x, s2.x);
+        s2.y = fmaf(vs.y, (x.y - cmean.y) * cinv.y, s2.y);
+        s2.z = fmaf(vs.z, (x.z - cmean.z) * cinv.z, s2.z);
+        s2.w = fmaf(vs.w, (x.w - cmean.w) * cinv.w, s2.w);
+        float* dst = ok ? cbase + 8 * i * LBW : g.dump + 4 * c4;
         if (NT) kd_st4_nt(dst, v); else kd_st4(dst, v);
       }
     };
-#ifdef KD_LB_DBG
-    unsigned long long dbg_acc[5] = {0, 0, 0, 0, 0}, dbg_t = __builtin_amdgcn_s_memtime();
-#endif
     // One step.  Issue order = the order the results are needed in (the in-order vmcnt then leaves every younger operation in
     // flight); sched_barriers keep hipcc's scheduler from sinking the table loads below the prefetch of the two streams.
     auto step = [&](int it, auto set_tag) __attribute__((always_inline)) {
@@ -320,19 +290,15 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
       fetch_rows(chunk_at(it + 3), trq[S]);                              // rows of chunk it + 3: their tables are issued by the NEXT step
       __builtin_amdgcn_sched_barrier(0);
       epilogue(it - 1);                                                   // the matrix waves left (dy . W2) of chunk it - 1 one barrier ago
-      KD_LSTAMP(0);
       __builtin_amdgcn_sched_barrier(0);
       convert_store(last_at(it + 1), ry[S], ra[S], tvb[S], (it + 1) & 1);
-      KD_LSTAMP(1);
       __builtin_amdgcn_sched_barrier(0);
       load_tables(trq[S ^ 1], tvb[S ^ 1]);                               // tables of chunk it + 2 (rows fetched one step ago)
       __builtin_amdgcn_sched_barrier(0);
       load_rows4(g.Y2, chunk_at(it + 3), ry[S]);
       load_rows4(g.Y1, chunk_at(it + 3), ra[S]);
       __builtin_amdgcn_sched_barrier(0);
-      KD_LSTAMP(2);
       kd_lds_barrier();
-      KD_LSTAMP(3);
     };
 
     for (int i = tid; i < 4 * LBXF / 4; i += 256) kd_st4(ldx + 4 * i, kd_zero4());      // ldx and stage: finite from the first read on
@@ -362,9 +328,6 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
       step(it + 1, std::integral_constant<int, 0>{});
     }
     if (nit > 0) epilogue(it - 1);                                        // the last step's chunk (a padding iteration stores nothing)
-#ifdef KD_LB_DBG
-    if (lane == 0) for (int i = 0; i < 4; ++i) atomicAdd(&kd_lb_dbg[i], dbg_acc[i]);
-#endif
     // column sums of the eight row groups -> one slab row per workgroup (fixed order: deterministic)
     kd_lds_barrier();
     float* red = reinterpret_cast<float*>(smem_raw);                      // [8][2][128] floats over the (dead) planes
@@ -405,9 +368,6 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
         for (int q = 0; q < 16; ++q) acc[i][k][q] = 0.f;
     const int o_lane = 4 * h * LBW + col;                                // accumulator layout: register q is row (q & 3) + 8 (q >> 2) + 4 h
     const int a_row = r * LBW, a_kk = (h ^ lb_key(r)) << 3;              // A fragment of k-step u: row r, chunk (2u + h) ^ key(r)
-#ifdef KD_LB_DBG
-    unsigned long long dbg_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, dbg_t = __builtin_amdgcn_s_memtime();
-#endif
     __builtin_amdgcn_s_waitcnt(0x0F70);                                   // vmcnt(0): the W2^T loads (nothing pending at the loop)
     kd_lds_barrier();
     const int nit2 = (nit + 1) & ~1;
@@ -431,28 +391,19 @@ __global__ __launch_bounds__(512, 1) void lidar_l2_bwd_kernel(LbArgs g) {
           a[pl] = lb_tr_frag(buf + (3 + pl) * LBPL, 16 * ks, 64 * wk + 32 * ki, lane);
         }
 #pragma unroll
-        for (int t = 0; t < ((KD_LB_PROBE & 2) ? 1 : 6); ++t)
+        for (int t = 0; t < 6; ++t)
           dacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[PA[t]], Wb[u][PB[t]], dacc, 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < ((KD_LB_PROBE & 4) ? 1 : 6); ++t)
+        for (int t = 0; t < 6; ++t)
           acc[ni][ki] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d[PA[t]], a[PB[t]], acc[ni][ki], 0, 0, 0);
       }
-      KD_LSTAMP(4);
       // (dy . W2) of this chunk -> stage tile (accumulator layout: 32 consecutive floats per half wave, conflict-free); the
       // vector waves turn it into G1 during the next step
       float* sb = stage + (it & 1) * LBXF + o_lane;
 #pragma unroll
       for (int q = 0; q < 16; ++q) sb[((q & 3) + 8 * (q >> 2)) * LBW] = dacc[q];
-      KD_LSTAMP(5);
       kd_lds_barrier();
-      KD_LSTAMP(7);
-#ifdef KD_LB_DBG
-      dbg_acc[8] += 1;
-#endif
     }
-#ifdef KD_LB_DBG
-    if (lane == 0) for (int i = 4; i < 9; ++i) atomicAdd(&kd_lb_dbg[i], dbg_acc[i]);
-#endif
     kd_lds_barrier();                                                     // (the vector waves' reduction barriers)
     kd_lds_barrier();
     float* out = g.wslab + (size_t)b * (LBW * LBW);
@@ -890,13 +841,5 @@ int kd_lidar_l1_bwd(const float* G, int64_t ldg, const float* Y1, int64_t ldy, c
   return kd_slab_reduce_launch(m1slab, grid_x, (int64_t)4 * K0, m1_out, st);
 }
 
-#ifdef KD_LB_DBG
-int kd_lb_dbg_read(unsigned long long* out, int reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(kd_lb_dbg), sizeof(unsigned long long) * 16);
-  if (reset) { unsigned long long z[16] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(kd_lb_dbg), z, sizeof(z)); }
-  return 0;
-}
-#endif
 
 }  // extern "C"

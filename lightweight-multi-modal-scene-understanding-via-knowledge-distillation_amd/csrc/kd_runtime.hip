@@ -108,10 +108,7 @@ __global__ void slab_strided_sum_kernel(const float* __restrict__ slab, int ngro
 // Outputs of >= 64 MB are consumed by a later kernel long after they have left L2 / MALL: storing them non-temporally
 // keeps the caches for what IS re-read (weights, per-cell tables, the other operand's rows).  Measured +1.1 % on the
 // KD step from the GEMM outputs alone.
-int kd_nt_store(size_t bytes) {
-  static const int mode = [] { const char* e = getenv("KD_NT_STORE"); return e ? atoi(e) : 1; }();
-  return mode && bytes >= ((size_t)64 << 20);
-}
+int kd_nt_store(size_t bytes) { return bytes >= ((size_t)64 << 20); }
 
 int kd_slab_reduce_tall_launch(float* slab, int rows, int64_t n, float* out, hipStream_t st) {
   int group = 1;

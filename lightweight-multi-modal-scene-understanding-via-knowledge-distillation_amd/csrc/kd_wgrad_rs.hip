@@ -20,7 +20,6 @@
 #include "kd_gemm_args.h"
 
 #include <atomic>
-#include <cstdlib>
 
 int kd_gemm_split_mode();     // kd_gemm.hip
 
@@ -236,23 +235,8 @@ __global__ __launch_bounds__(RS_THREADS, 1) void pw_wgrad_rs_kernel(WgradArgs g,
   }
 }
 
-std::atomic<int> g_rs_on{-1};       // 0 off, 1 the layers where it measured faster (default), 2 every layer with an instance
-int rs_mode() {
-  int v = g_rs_on.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("KD_WGRAD_RS");
-    v = (e && e[0] == '0') ? 0 : ((e && e[0] == 'a') ? 2 : 1);
-    g_rs_on.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-
-bool rs_wide12() {
-  // twelve k-blocks per matrix wave for 128 x 384 (one slice) and 128 x 768 (two slices): the narrow operand is converted once / twice
-  // instead of twice / four times.  Measured at 256 frames: 220 -> 192 us and 418 -> 364 us (profiles/r04_wgrad_rs_ab.txt); =0 restores six.
-  static const bool on = [] { const char* e = getenv("KD_WGRAD_RS_WIDE12"); return !(e && e[0] == '0'); }();
-  return on;
-}
+std::atomic<int> g_rs_on{1};        // 0 off, 1 the layers where it measured faster (default), 2 every layer with an instance
+int rs_mode() { return g_rs_on.load(std::memory_order_relaxed); }
 
 // ---- configuration table ------------------------------------------------------------------------------------------------
 struct RsPlan { int tnw, tkw, wn, wk, chk, ncs, split_n; };
@@ -261,11 +245,13 @@ struct RsPlan { int tnw, tkw, wn, wk, chk, ncs, split_n; };
 bool rs_plan(int N, int K, RsPlan& p, bool any = false) {
   if (N % 32 || K % 32) return false;
   int nb = N / 32, kb = K / 32, ncs = 1, split_n = 0;
-  // the 768-wide operand is cut into column slices so that a workgroup's block of dW fits its accumulator registers
+  // the 768-wide operand is cut into column slices so that a workgroup's block of dW fits its accumulator registers.  128 x 384 and
+  // 128 x 768 run twelve k-blocks per matrix wave (one / two slices): the narrow operand is converted once / twice instead of twice /
+  // four times with six.  Measured at 256 frames: 220 -> 192 us and 418 -> 364 us (profiles/r04_wgrad_rs_ab.txt).
   if (nb == 24) { nb = 8; ncs = 3; split_n = 1; }
-  else if (kb == 24 && nb == 4 && rs_wide12()) { kb = 12; ncs = 2; }
+  else if (kb == 24 && nb == 4) { kb = 12; ncs = 2; }
   else if (kb == 24) { kb = 6; ncs = 4; }
-  else if (kb == 12 && nb == 4 && rs_wide12()) { }
+  else if (kb == 12 && nb == 4) { }
   else if (kb == 12 && nb <= 4) { kb = 6; ncs = 2; }
   else if (nb == 8 && kb == 8) { nb = 4; ncs = 2; split_n = 1; }
   struct E { int nb, kb, tnw, tkw, wn, wk, chk; };
@@ -274,8 +260,7 @@ bool rs_plan(int N, int K, RsPlan& p, bool any = false) {
       {12, 2, 3, 2, 4, 1, 1},   // 384 x 64   stage-3 / 4 expand
       {8, 4, 2, 4, 4, 1, 1},    // 768 x 128  stage-5 expand (3 column slices of 256)
       {2, 6, 1, 3, 2, 2, 2},    // 64 x 192 stage-2 project; 64 x 384 stage-3 project (2 slices)
-      {4, 6, 1, 6, 4, 1, 2},    // 128 x 384 stage-4 project (2 slices); 128 x 768 stage-5 project (4 slices)
-      {4, 12, 1, 12, 4, 1, 1},  // 128 x 384 stage-4 project (one slice); 128 x 768 stage-5 project (2 slices): twelve k-blocks per wave (default)
+      {4, 12, 1, 12, 4, 1, 1},  // 128 x 384 stage-4 project (one slice); 128 x 768 stage-5 project (2 slices)
       {4, 4, 2, 2, 2, 2, 2},    // 128 x 128  FPN laterals / post, fusion projections
       {4, 2, 2, 1, 2, 2, 2},    // 128 x 64   FPN lateral of stage 3
       {2, 4, 1, 2, 2, 2, 2},    // 64 x 128   head block 0
@@ -285,12 +270,12 @@ bool rs_plan(int N, int K, RsPlan& p, bool any = false) {
   // Measured per layer at 256 frames against pw_wgrad_kernel (tools/bench_wgrad.py, profiles/r04_wgrad_rs_ab.txt): x1.28 (192 x 32),
   // x1.08-1.10 (384 x 64, 768 x 128, 64 x 384), x1.20 (128 x 384), x1.02 (128 x 768), x1.04 (128 x 256), x1.13 (256 x 256); it LOSES
   // on 64 x 192 (x0.95), 128 x 128 (x0.91), 64 x 256 (x0.97) and ties on 64 x 128 / 128 x 64 -- those stay on the tiled kernel
-  // unless kd_set_wgrad_rs(2) / KD_WGRAD_RS=all (tests exercise every instance that way).
+  // unless kd_set_wgrad_rs(2) (tests exercise every instance that way).
   const bool all = any || rs_mode() == 2;
   for (const E& e : tab)
     if (e.nb == nb && e.kb == kb) {
       const bool wins = (nb == 4 && kb == 12) || (nb == 6 && kb == 1) || (nb == 12 && kb == 2) || (nb == 8 && kb == 4) || (nb == 2 && kb == 6 && ncs == 2) ||
-                        (nb == 4 && kb == 6) || (nb == 4 && kb == 8);
+                        (nb == 4 && kb == 8);
       if (!wins && !all) return false;
       p = {e.tnw, e.tkw, e.wn, e.wk, e.chk, ncs, split_n};
       return true;
@@ -329,7 +314,7 @@ int rs_slices(int64_t M, const RsPlan& p) {
 
 }  // namespace
 
-extern "C" int kd_set_wgrad_rs(int mode) { const int prev = rs_mode(); g_rs_on.store(mode < 0 ? 0 : (mode > 2 ? 2 : mode), std::memory_order_relaxed); return prev; }
+extern "C" int kd_set_wgrad_rs(int mode) { return g_rs_on.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode)); }
 
 // (sized for the role-specialised form whenever the layer HAS one, whatever the switches say now: a workspace allocated before a
 // switch flips must still fit)
@@ -354,8 +339,7 @@ int kd_wgrad_rs_launch(const WgradArgs& g0, size_t ws_bytes, float* dW, hipStrea
   q.nrs = (int)(((int64_t)g.M + q.rows_per_slice - 1) / q.rows_per_slice);
   int rc = 0;
 #define KD_RS_SHAPE(A_, B_, C_, D_, E_) if (p.tnw == A_ && p.tkw == B_ && p.wn == C_ && p.wk == D_ && p.chk == E_) rc = rs_launch_shape<A_, B_, C_, D_, E_>(g, q, st);
-  KD_RS_SHAPE(3, 1, 2, 1, 2) KD_RS_SHAPE(3, 2, 4, 1, 1) KD_RS_SHAPE(2, 4, 4, 1, 1) KD_RS_SHAPE(1, 3, 2, 2, 2) KD_RS_SHAPE(1, 6, 4, 1, 2)
-  KD_RS_SHAPE(1, 12, 4, 1, 1)
+  KD_RS_SHAPE(3, 1, 2, 1, 2) KD_RS_SHAPE(3, 2, 4, 1, 1) KD_RS_SHAPE(2, 4, 4, 1, 1) KD_RS_SHAPE(1, 3, 2, 2, 2) KD_RS_SHAPE(1, 12, 4, 1, 1)
   KD_RS_SHAPE(2, 2, 2, 2, 2) KD_RS_SHAPE(2, 1, 2, 2, 2) KD_RS_SHAPE(1, 2, 2, 2, 2) KD_RS_SHAPE(2, 4, 2, 2, 1) KD_RS_SHAPE(1, 4, 2, 2, 2)
 #undef KD_RS_SHAPE
   if (rc <= 0) return rc;

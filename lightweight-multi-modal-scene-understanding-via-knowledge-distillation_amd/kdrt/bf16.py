@@ -21,9 +21,7 @@ from .lib import KDError, lib
 from .ops import ACT_RELU, ACT_RELU6, P, stream
 
 
-import os as _os
-
-_LIDAR_ONE_KERNEL = _os.environ.get("KD_BF16_LIDAR_ONE_KERNEL", "1") != "0"
+_LIDAR_ONE_KERNEL = True          # False: the LiDAR encoder layer by layer (tests compare the two)
 
 
 def _coef(spec):

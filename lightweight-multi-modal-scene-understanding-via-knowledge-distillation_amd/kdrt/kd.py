@@ -24,13 +24,13 @@ class KDStep:
     def __init__(self, student, teacher, optimizer: FusedAdamW, class_weights: Optional[torch.Tensor] = None,
                  T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
                  reducer: Optional[BucketedAllReduce] = None, teacher_storage: str = "fp32",
-                 fused_objective: Optional[bool] = None):
+                 fused_objective: bool = True):
         if teacher_storage not in ("fp32", "bf16"):
             raise ValueError(f"teacher_storage must be 'fp32' or 'bf16', got {teacher_storage!r}")
         # fused objective (default): loss values and loss gradients from the same kernel passes, feature-MSE gradients added
-        # inside the fusion block's data-gradient GEMMs (losses.kd_objective_backward); False / KD_FUSED_OBJECTIVE=0 keeps the
+        # inside the fusion block's data-gradient GEMMs (losses.kd_objective_backward); False keeps the
         # autograd formulation kd_objective(...).backward() -- same bits, more passes (tests compare the two)
-        self.fused_objective = (os.environ.get("KD_FUSED_OBJECTIVE", "1") != "0") if fused_objective is None else bool(fused_objective)
+        self.fused_objective = bool(fused_objective)
         # "bf16": the frozen teacher runs kdrt.bf16.forward_bf16 (bf16 activations in HBM, fp32 accumulate); a second,
         # separately gated mode -- the default keeps every tensor of the step fp32
         self.teacher_storage = teacher_storage

@@ -347,7 +347,7 @@ class TransposeCache:
         self.entries = {}          # (data_ptr, R, C) -> [weight view, W^T buffer, stamp, weakref to the owning parameter]
         self.table = None
         self.nblocks = 0
-        self.enabled = _os.environ.get("KD_TRANSPOSE_CACHE", "1") != "0"
+        self.enabled = True
 
     @staticmethod
     def _stamp(e):

@@ -53,7 +53,6 @@ def stale_cache_guard(module):
 
 
 _EVAL_COEFF_CACHE = os.environ.get("KD_EVAL_COEFF_CACHE", "1") != "0"
-_DW_BWD_ADD = os.environ.get("KD_DW_BWD_ADD", "1") != "0"        # 0: residual gradient of a depthwise-first block added by a separate pass
 
 
 def _coeffs(spec: UnitSpec, partial, rows, C, count, training, bnc=None, device=None):
@@ -220,8 +219,8 @@ def pw_forward_final(spec: UnitSpec, inp: Operand, res: Optional[torch.Tensor] =
 # widest tensor of an InvertedResidual / DWSeparableConv, is never written.  Measured inside the KD step at 256 frames
 # (profiles/r02_dw_pw_fusion.txt): the one-kernel form wins where the hidden tensor is wide and the output narrow (stage 2:
 # 192 -> 64 at stride 2, 1065 -> 916 us; stage 3: 384 -> 64, 1211 -> 1085 us) and loses elsewhere (its 128-pixel tiles expose one
-# HBM latency per 32-channel chunk), so mode 1 (default) uses it for those shapes only.  KD_DW_PW_FUSED: 0 never, 1 by shape, 2 always.
-DW_PW_FUSED = [int(os.environ.get("KD_DW_PW_FUSED", "1"))]
+# HBM latency per 32-channel chunk), so mode 1 (default) uses it for those shapes only.  DW_PW_FUSED: 0 never, 1 by shape, 2 always.
+DW_PW_FUSED = [1]
 
 
 def dw_pw_tail_ok(units, cur: Operand) -> bool:
@@ -314,9 +313,9 @@ def unit_backward(rec: _Rec, g, need_input_grad: bool = True, addend: Optional[t
         inp = rec.inp
         N, K = C, inp.C
         dW, w_dir = gradsink.out_for(rec.w)
-        fused = (tables and need_input_grad and addend is None and _LIDAR_FUSED_BWD and lib.kd_lidar_l2_bwd_supported(N, K)
+        fused = (tables and need_input_grad and addend is None and lib.kd_lidar_l2_bwd_supported(N, K)
                  and ld(y) == N and ld(inp.raw) == K)               # (dense operands: the one-kernel form addresses rows by 128)
-        fused1 = (inp.virt is not None and need_input_grad and addend is None and _LIDAR_FUSED_BWD and _L0_MOMENTS and not tables
+        fused1 = (inp.virt is not None and need_input_grad and addend is None and not tables
                   and mact == ACT_NONE and inp.act == ACT_RELU and lib.kd_lidar_l1_bwd_supported(N, K) and ld(t) == N and ld(y) == N)
         if fused or fused1:
             pass            # data gradient and weight gradient in one kernel, below
@@ -340,17 +339,11 @@ def unit_backward(rec: _Rec, g, need_input_grad: bool = True, addend: Optional[t
                     raise KDError("addend on a virtual LiDAR layer-0 input is not supported")
                 rows_in = lib.kd_lidar_l1_dgrad_stat_rows(M, N, K)
                 part_in = torch.empty(rows_in * 2 * K, device=dev, dtype=torch.float32)
-                if _L0_MOMENTS:
-                    # layer 0's weight gradient is linear in G0: the GEMM epilogue leaves sum G0 * point and G0 is never written
-                    m1 = torch.empty(4, K, device=dev, dtype=torch.float32)
-                    ops.l1_dgrad(t, y, Wt, None, op=inp, al=al, be=be, ga=ga, msc=msc, msh=msh, mact=mact, partial=part_in,
-                                 partial_rows=rows_in, moments=m1)
-                    g_in = ("GM", m1, part_in, rows_in)
-                else:
-                    gin = torch.empty(M, K, device=dev, dtype=torch.float32)
-                    ops.l1_dgrad(t, y, Wt, gin, op=inp, al=al, be=be, ga=ga, msc=msc, msh=msh, mact=mact, partial=part_in,
-                                 partial_rows=rows_in)
-                    g_in = ("G", gin, part_in, rows_in)
+                # layer 0's weight gradient is linear in G0: the GEMM epilogue leaves sum G0 * point and G0 is never written
+                m1 = torch.empty(4, K, device=dev, dtype=torch.float32)
+                ops.l1_dgrad(t, y, Wt, None, op=inp, al=al, be=be, ga=ga, msc=msc, msh=msh, mact=mact, partial=part_in,
+                             partial_rows=rows_in, moments=m1)
+                g_in = ("GM", m1, part_in, rows_in)
             elif fused:
                 gin = torch.empty(M, K, device=dev, dtype=torch.float32)
                 rows_in = lib.kd_lidar_l2_bwd_stat_rows(M)
@@ -394,7 +387,7 @@ def unit_backward(rec: _Rec, g, need_input_grad: bool = True, addend: Optional[t
                 rows_in = lib.kd_dwconv_bwd_stat_rows(inp.M, C)
                 part_in = torch.empty(rows_in * 2 * C, device=dev, dtype=torch.float32)
         # a residual gradient into the same input rides inside the kernel where the one-pass form allows it (round 3)
-        add_in_kernel = (addend is not None and need_input_grad and _DW_BWD_ADD and ld(addend) == C
+        add_in_kernel = (addend is not None and need_input_grad and ld(addend) == C
                          and lib.kd_dwconv3x3_bwd_add_supported(C, W, s))
         if add_in_kernel:
             lib.call("kd_dwconv3x3_bwd_add", P(t), P(y), P(al), P(be), P(ga), P(msc), P(msh), mact, P(inp.raw), P(inp.sc),
@@ -480,7 +473,7 @@ def chain_backward(recs: Sequence[_Rec], g, need_input_grad=True, first_addend=N
     return all_grads, g
 
 
-_STEM_INFER = os.environ.get("KD_STEM_INFER", "1") != "0"       # 0: stem conv and its BatchNorm + activation as two passes also in inference
+_STEM_INFER = True       # False: stem conv and its BatchNorm + activation as two passes also in inference
 
 
 def stem_infer(spec: UnitSpec, img):
@@ -599,7 +592,7 @@ class PairChainFn(torch.autograd.Function):
         return (dx, None, None, None, *grads_a, *grads_b)
 
 
-_CHAIN_PAIRS = os.environ.get("KD_CHAIN_PAIRS", "1") != "0"
+_CHAIN_PAIRS = True      # False: every chain pair as two separate chains (tests compare the two)
 _GRAD_ROUTING = os.environ.get("KD_GRAD_ROUTING", "1") != "0"     # 0: two-consumer feature gradients summed by autograd
 
 
@@ -620,7 +613,7 @@ def chain_pair_ok(units_a: Sequence[UnitSpec], units_b: Sequence[UnitSpec], trai
     first = units_b[0]
     if first.kind == "dw":
         C = first.conv.weight.shape[0]
-        return bool(_DW_BWD_ADD and first.stride == 1 and lib.kd_dwconv3x3_bwd_add_supported(C, out_w, 1))
+        return bool(first.stride == 1 and lib.kd_dwconv3x3_bwd_add_supported(C, out_w, 1))
     return True
 
 
@@ -1012,17 +1005,12 @@ def run_x4_head(x, units, cls_conv, training):
 # =================================================================================================
 # training scatter-max: "sorted" (cell-sorted segments, default) or "atomic" (kept for A/B and for widths the
 # segmented kernels do not cover)
-_SCATTER_MODE = os.environ.get("KD_SCATTER", "sorted")
+_SCATTER_MODE = "sorted"
 # with sorted points: hand the scatter-max gradient to the last layer's backward GEMMs as per-cell tables (default) or
-# as the materialised [points, C] tensor ("0": A/B and tests)
-_SCATTER_TABLES = os.environ.get("KD_SCATTER_TABLES", "1") != "0"
-# layer 0's gradient through moments of G0 accumulated in the layer-1 dgrad epilogue (default) or through the stored G0
-_L0_MOMENTS = os.environ.get("KD_L0_MOMENTS", "1") != "0"
-# one backward kernel per point-MLP layer (data + weight gradient from one read of the operands, csrc/kd_lidar_bwd.hip);
-# "0": the separate dgrad / wgrad GEMM launches of round 2 (A/B and tests)
-_LIDAR_FUSED_BWD = os.environ.get("KD_LIDAR_FUSED_BWD", "1") != "0"
-# the whole eval-mode encoder (point MLP + scatter-max) in one kernel (csrc/kd_lidar_infer.hip); "0": layer by layer
-_LIDAR_FUSED_INFER = os.environ.get("KD_LIDAR_FUSED_INFER", "1") != "0"
+# as the materialised [points, C] tensor (False: tests)
+_SCATTER_TABLES = True
+# the whole eval-mode encoder (point MLP + scatter-max) in one kernel (csrc/kd_lidar_infer.hip); False: layer by layer
+_LIDAR_FUSED_INFER = True
 
 
 _sort_cache: dict = {}

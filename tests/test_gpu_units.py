@@ -560,7 +560,7 @@ def test_chain_pairs_match_separate_chains(monkeypatch):
 
 def test_stem_inference_kernel_same_bits_as_two_passes(monkeypatch):
     """Inference (eval, no autograd): the stem's conv + BatchNorm + ReLU6 run as ONE kernel (kd_stem_conv_fwd_infer); with
-    KD_STEM_INFER=0 as conv + kd_bn_act_apply.  Same operations in the same order: every multiscale map has the same bits."""
+    _STEM_INFER = False as conv + kd_bn_act_apply.  Same operations in the same order: every multiscale map has the same bits."""
     from kdrt import units
     from src.models.camera_encoder import TwinLiteEncoder
     torch.manual_seed(4)

@@ -6,7 +6,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
-#include <dlfcn.h>
 #include <cmath>
 #include <vector>
 #include "kd_hip.h"
@@ -76,15 +75,6 @@ int main(int argc, char** argv) {
       double md = 0, mv = 0;
       for (size_t i = 0; i < n; ++i) { md = std::max(md, (double)fabsf(r1[i] - r0[i])); mv = std::max(mv, (double)fabsf(r0[i])); }
       printf("    split vs fp32 forward: max|diff| %.3e, max|value| %.3e, ratio %.2e\n", md, mv, md / mv);
-    }
-    if (auto rd = (int (*)(unsigned long long*, int))dlsym(RTLD_DEFAULT, "kd_dbg_read")) {   // dev build with phase counters
-      unsigned long long c[8];
-      rd(c, 1);
-      RC(kd_pwconv_gemm(A, s.K, nullptr, 0, 1, 2, sc, sh, nullptr, nullptr, nullptr, W, nullptr, C, s.N, nullptr, 0, 1, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, partial, kd_pwconv_stat_rows_for(s.M, s.K, s.N, 1, 1, 0), s.M, s.K, s.N, nullptr, nullptr));
-      rd(c, 1);
-      const double t = (double)c[6];
-      printf("    phases (cycles/tile, wave 0): load-wait+transform %.0f | barrier %.0f | split+LDS %.0f | barrier %.0f | MFMA %.0f | epilogue %.0f | tiles %.0f\n",
-             c[0] / t, c[1] / t, c[2] / t, c[3] / t, c[4] / t, c[5] / t, t);
     }
     float tc = timeit([&] { hipLaunchKernelGGL(copy_kernel, dim3(2048), dim3(256), 0, 0, (const float4*)A, (float4*)C, (size_t)s.M * s.K / 4, (size_t)s.M * s.N / 4); });
     printf("%-25s %8ld | %7.1fus %5.1fTF %4.2fTB/s | %7.1fus %5.1fTF | %7.1fus %5.1fTF %4.2fTB/s | %7.1fus %5.1fTF %4.2fTB/s | %7.1fus %4.2fTB/s\n", s.name, s.M,

@@ -67,15 +67,3 @@ if which in ("both", "separate"):
 if which in ("both", "fused"):
     t = timeit(fused)
     print(f"one kernel                      : {t:7.3f} ms  ({gb / t * 1e3:.0f} GB/s of its 3 tensor passes, {2 * 2.0 * M * C * C / t / 1e9:.0f} TFLOP/s fp32-equivalent)", flush=True)
-if hasattr(lib._dll, "kd_lb_dbg_read"):          # instrumented build (KD_HIP_LIB=tools/dbg/lb/libkd_hip.so)
-    import ctypes
-    buf = (ctypes.c_ulonglong * 16)()
-    lib._dll.kd_lb_dbg_read(buf, 1)
-    fused(); torch.cuda.synchronize()
-    lib._dll.kd_lb_dbg_read(buf, 1)
-    its = max(buf[8], 1)                        # iterations summed over role-A waves
-    names = ["V: rows fetch + epilogue", "V: convert + LDS stores", "V: issue loads", "V: barrier", "M: both k-loops", "M: stage stores", "-", "M: barrier"]
-    print("per-iteration cycles (s_memtime, averaged over the waves of the role):")
-    for i, n in enumerate(names):
-        print(f"  {n:28s} {buf[i] / its:8.0f}")
-    print(f"  V total {sum(buf[0:4]) / its:.0f}   M total {sum(buf[4:8]) / its:.0f}")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Dev tool: kd_stem_conv_fwd alone at the benchmarked size (256 frames, 3 x 256 x 256 -> 128 x 128 x 32), HIP-event timed, with and without the
-BatchNorm-statistics slab; KD_HIP_LIB selects a probe build (tools/dbg/stem/libkd_p<bits>.so, -DKD_STEM_PROBE).  usage: bench_stem.py [frames]"""
+BatchNorm-statistics slab.  usage: bench_stem.py [frames]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lightweight-multi-modal-scene-understanding-via-knowledge-distillation_amd"))
@@ -21,4 +21,4 @@ def t(p):
         lib.call("kd_stem_conv_fwd", P(x), P(w), P(y), p, B, 3, 256, 256, 32, stream())
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / 10 * 1e3
-print(os.environ.get("KD_HIP_LIB", "default lib"), f"eval {t(None):7.1f} us   train(+stats) {t(P(part)):7.1f} us")
+print(f"eval {t(None):7.1f} us   train(+stats) {t(P(part)):7.1f} us")

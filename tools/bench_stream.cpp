@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <cmath>
 #include <vector>
-#include <dlfcn.h>
 #include "kd_hip.h"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
@@ -74,13 +73,6 @@ int main(int argc, char** argv) {
       const long rows1 = kd_pwconv_stat_rows_for(s.M, s.K, s.N, s.kind ? 3 : 1, epi, 0);
       CK(hipMemset(C, 0xee, (size_t)s.M * s.N * 4));
       float t_new = timeit([&] { run(C, partial); });
-      if (auto rd = (int (*)(unsigned long long*, int))dlsym(RTLD_DEFAULT, "kd_stream_dbg_read")) {   // dev build with phase stamps
-        unsigned long long c[8];
-        rd(c, 1); run(C, partial); rd(c, 1);
-        const double sl = (double)c[3], nw = (double)c[5];
-        if (sl > 0) printf("    phases per slab (cycles): load wait + conv0 %.0f | k-loop %.0f | next loads + epilogue %.0f | slabs/wave %.1f | wave lifetime %.1f us\n",
-                           c[0] / sl, c[1] / sl, c[2] / sl, sl / nw, c[4] / nw / 100.0);
-      }
       // compare
       const size_t n = (size_t)s.M * s.N;
       std::vector<float> r0(std::min(n, (size_t)1 << 24)), r1(r0.size());

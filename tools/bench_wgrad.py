@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Dev tool: the camera weight-gradient GEMMs of the KD step (kd_pwconv_wgrad, BN-backward on D, BN + act on A) at the benchmarked size
-(256 frames), HIP-event timed; KD_HIP_LIB selects a probe build (-DKD_WG_PROBE).  usage: bench_wgrad.py [frames]"""
+(256 frames), HIP-event timed.  usage: bench_wgrad.py [frames]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "lightweight-multi-modal-scene-understanding-via-knowledge-distillation_amd"))
@@ -14,7 +14,6 @@ shapes = [("stage2 expand 32->192 @128^2", 128 * 128, 32, 192), ("stage2 project
           ("fpn lateral 64->128", 64 * 64, 64, 128), ("head (concat) 256->64", 64 * 64, 256, 64)]
 g = torch.Generator(device="cuda").manual_seed(1)
 v = lambda n: torch.rand(n, device="cuda", generator=g) + 0.5
-print(os.environ.get("KD_HIP_LIB", "default lib"))
 tot = [0.0, 0.0]
 for name, hw, K, N in shapes:
     M = B * hw
