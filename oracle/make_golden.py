@@ -42,6 +42,15 @@ def digest(t: torch.Tensor) -> np.ndarray:
     return np.concatenate([[t.sum().item(), t.norm().item(), t.abs().max().item()], head.numpy()])
 
 
+PROJ_SEED = 20261016
+
+
+def grad_projections(seed: int, index: int, numel: int) -> torch.Tensor:
+    """[4, numel] float64 N(0, 1) directions for parameter number `index` (named_parameters order); the tests rebuild them."""
+    g = torch.Generator().manual_seed(seed * 1000 + index)
+    return torch.randn(4, numel, generator=g, dtype=torch.float64)
+
+
 def build(ref_mods, fusion, out_ch, num_classes=2, grid=16, output_mode="same"):
     cam_m, lid_m, fus_m = ref_mods
     cam = cam_m.TwinLiteEncoder(return_multiscale=True)
@@ -169,6 +178,12 @@ def section_headline(mods, out_dir):
                    ("lidar_w0", "lidar_encoder.encoder.point_mlp.0.weight"), ("lidar_w6", "lidar_encoder.encoder.point_mlp.6.weight"),
                    ("stage3_proj_w", "camera_encoder.stage3.conv.6.weight")):
         out["kd_grad64_" + tag] = g64[n].numpy().copy()
+    # element-wise pins for EVERY tensor at a few bytes each: four fixed Gaussian projections <g, r_k> of the float64 and of
+    # the fp32 gradient (a permuted or sign-flipped gradient keeps its norm but moves each projection by ~sqrt(2)*|g|)
+    out["kd_grad_proj_seed"] = np.int64(PROJ_SEED)
+    r = [grad_projections(PROJ_SEED, i, g64[n].numel()) for i, n in enumerate(names)]
+    out["kd_grad_proj64"] = np.stack([(rk @ g64[n].reshape(-1)).numpy() for rk, n in zip(r, names)])
+    out["kd_grad_proj32_reference"] = np.stack([(rk @ g32[n].reshape(-1)).numpy() for rk, n in zip(r, names)])
     del t64, s64, zs64, ms64, zt64, mt64
     # the reference trainer's own step on the same batch (CE only), fresh statistics
     student.load_state_dict(st_s)

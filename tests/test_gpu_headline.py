@@ -9,6 +9,7 @@ import torch
 import kd_oracle as O
 from _gpu_util import FUSIONS, build_product, load_random_state, max_err
 from _util import digest, digest_close, golden
+from make_golden import grad_projections
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("gemm_arith")]
 TOL = 1e-4
@@ -114,6 +115,18 @@ def test_headline_frame_shape_kd_step_against_the_reference():
         d = abs(grads[k].norm().item() - norm64[k])
         # (absolute floor: the 2-element attention bias is a cancelling sum of norm 4e-4 -- its fp32 error is rounding of the terms)
         if d > (3 * ref_err[k] + 1e-5) * norm64[k] + 2e-5 * gmax:
+            bad.append((k, d / norm64[k], ref_err[k]))
+    assert not bad, bad
+    # every tensor element-wise as well: four fixed Gaussian projections <g, r_k> against the float64 ones.  For an error e,
+    # <e, r_k> ~ N(0, |e|^2); 5 is its tail bound -- a permuted or sign-flipped gradient misses by ~sqrt(2)*|g|
+    proj64, seed = gd["kd_grad_proj64"], int(gd["kd_grad_proj_seed"])
+    bad = []
+    for i, k in enumerate(names):
+        if norm64[k] < 1e-6 * gmax:
+            continue
+        got = (grad_projections(seed, i, grads[k].numel()) @ grads[k].reshape(-1)).numpy()
+        d = np.abs(got - proj64[i]).max()
+        if d > 5 * (3 * ref_err[k] + 1e-5) * norm64[k]:
             bad.append((k, d / norm64[k], ref_err[k]))
     assert not bad, bad
 

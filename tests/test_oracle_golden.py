@@ -6,6 +6,7 @@ import torch
 
 import kd_oracle as O
 from _util import digest, digest_close, golden, state_template
+from make_golden import grad_projections
 
 FUSIONS = ("concat", "minimal", "weighted")
 B, HW, N, G = 2, 64, 512, 16
@@ -268,6 +269,17 @@ def test_headline_workload_kd_and_ce_step():
         want = torch.from_numpy(gd["kd_grad64_" + tag])
         err = ((s_st[k].grad.double() - want).norm() / want.norm()).item()
         assert err <= 3 * ref_err[k] + 1e-6, (k, err, ref_err[k])
+    # element-wise pins of every tensor (projections on fixed Gaussian directions, tests/test_gpu_headline.py): the fp32
+    # reference meets the GPU test's bound with its own error, the oracle with three times it
+    norm64, proj64, seed = gd["kd_grad_norm64"], gd["kd_grad_proj64"], int(gd["kd_grad_proj_seed"])
+    gmax = norm64.max()
+    for i, k in enumerate(keys):
+        if norm64[i] < 1e-6 * gmax:
+            continue
+        bound = 5 * (ref_err[k] + 1e-5) * norm64[i]
+        assert np.abs(gd["kd_grad_proj32_reference"][i] - proj64[i]).max() <= bound, k
+        got = (grad_projections(seed, i, s_st[k].grad.numel()) @ s_st[k].grad.double().reshape(-1)).numpy()
+        assert np.abs(got - proj64[i]).max() <= 5 * (3 * ref_err[k] + 1e-5) * norm64[i], k
     for k, want in zip(gd["buf_keys"], gd["buf_digest"]):
         assert digest_close(digest(s_st[str(k)].float()), want), str(k)
     s2 = _state("weighted", 12, grad=True)
