@@ -92,7 +92,8 @@ int kd_transpose_batch(const int64_t* table, int n, int nblocks, void* stream);
 int kd_copy_segments(const float* s0, float* d0, int64_t n0, const float* s1, float* d1, int64_t n1, const float* s2, float* d2,
                      int64_t n2, const float* s3, float* d3, int64_t n3, void* stream);
 
-/* ---- stem 3x3/s2 conv (camera_encoder.py:63-67), NCHW image in, NHWC raw out, Cout == 32 ---- */
+/* ---- stem 3x3/s2 conv (camera_encoder.py:63-67), NCHW image in, NHWC raw out, Cout in {8, 16, 24, 32, 40}
+ * (TwinLiteEncoder base_channels; any other Cout: KD_ERR_SHAPE), Cin 1..4; the statistics slab is [rows][2][Cout] ---- */
 int64_t kd_stem_stat_rows(int64_t npix_out);
 int kd_stem_conv_fwd(const float* x_nchw, const float* w, float* y_nhwc, float* partial, int B, int Cin, int H,
                      int W, int Cout, void* stream);
@@ -393,7 +394,9 @@ int kd_dw_pw_infer(const float* x, const float* isc, const float* ish, int iact,
  * fusion_module.py:12,29, lidar_encoder.py:26-34 incl. the scatter-max of :85-96), the FPN resize + sum (:58-63) and the
  * classifier (:170).  kd_bf16_pwconv: a_kind 0 = A bf16, 1 = A fp32 (rounded on load), 3 = A are LiDAR points [M][4] and
  * layer 0 (l0w [K][4], l0b, sc0, sh0, act0) is recomputed; epi 0 = C bf16 (+ res bf16), 4 = scatter-max of the
- * non-negative result into the zero-filled fp32 grid [cells][ldgrid] by cell[m] (< 0: skipped). */
+ * non-negative result into the zero-filled fp32 grid [cells][ldgrid] by cell[m] (< 0: skipped).  K and N are multiples of 8,
+ * K <= 1024 (multiples of 32 run the full-tile kernels; others a zero-padded, column-masked tile).  kd_bf16_stem: Cout in
+ * {8, 16, 24, 32, 40}.  kd_bf16_dwconv3x3: C a multiple of 8, C <= 1024. */
 int kd_bf16_stem(const float* x_nchw, const float* w, const float* sc, const float* sh, int act, void* y, int B, int Cin, int H,
                  int W, int Cout, void* stream);
 int kd_bf16_dwconv3x3(const void* x, const float* w, const float* sc, const float* sh, int act, void* y, int B, int H, int W,

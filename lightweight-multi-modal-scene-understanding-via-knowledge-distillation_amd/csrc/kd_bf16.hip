@@ -40,20 +40,22 @@ __device__ __forceinline__ u32x4 ld16(const bf16_t* p) { return *reinterpret_cas
 __device__ __forceinline__ void st16(bf16_t* p, u32x4 v) { *reinterpret_cast<u32x4*>(p) = v; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// stem: 3x3 / s2 dense conv on the NCHW fp32 image, Cout == 32 (camera_encoder.py:63-67) -> act(bn(.)) as bf16 NHWC.
+// stem: 3x3 / s2 dense conv on the NCHW fp32 image, Cout == COUT (camera_encoder.py:63-67) -> act(bn(.)) as bf16 NHWC.
+// COUT: the stem width (TwinLiteEncoder base_channels), 8, 16, 24, 32 or 40.
+template <int COUT>
 __global__ __launch_bounds__(256) void stem_bf16_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ sc,
                                                         const float* __restrict__ sh, int act, bf16_t* __restrict__ y, int B, int Cin,
                                                         int H, int W, int Ho, int Wo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int KK = Cin * 9;
-  float* ws = sm;                      // [KK][32] tap-major
-  for (int i = threadIdx.x; i < KK * 32; i += 256) ws[(i % KK) * 32 + i / KK] = w[i];
+  float* ws = sm;                      // [KK][COUT] tap-major
+  for (int i = threadIdx.x; i < KK * COUT; i += 256) ws[(i % KK) * COUT + i / KK] = w[i];
   __syncthreads();
   const int64_t npix = (int64_t)B * Ho * Wo;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (int64_t)gridDim.x * 256) {
-    float acc[32];
+    float acc[COUT];
 #pragma unroll
-    for (int c = 0; c < 32; ++c) acc[c] = 0.f;
+    for (int c = 0; c < COUT; ++c) acc[c] = 0.f;
     const int wo = (int)(p % Wo), ho = (int)((p / Wo) % Ho), b = (int)(p / ((int64_t)Wo * Ho));
     for (int ci = 0; ci < Cin; ++ci) {
       const float* xp = x + ((int64_t)b * Cin + ci) * H * W;
@@ -65,15 +67,15 @@ __global__ __launch_bounds__(256) void stem_bf16_kernel(const float* __restrict_
           const int wi = 2 * wo - 1 + kw;
           float v = 0.f;
           if (hi >= 0 && hi < H && wi >= 0 && wi < W) v = xp[(int64_t)hi * W + wi];
-          const float* wt = ws + (ci * 9 + kh * 3 + kw) * 32;
+          const float* wt = ws + (ci * 9 + kh * 3 + kw) * COUT;
 #pragma unroll
-          for (int c = 0; c < 32; ++c) acc[c] = fmaf(v, wt[c], acc[c]);
+          for (int c = 0; c < COUT; ++c) acc[c] = fmaf(v, wt[c], acc[c]);
         }
       }
     }
-    bf16_t* yp = y + p * 32;
+    bf16_t* yp = y + p * COUT;
 #pragma unroll
-    for (int c = 0; c < 32; c += 8) {
+    for (int c = 0; c < COUT; c += 8) {
       float o[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = kd_act(kd_affine(acc[c + j], sc[c + j], sh[c + j]), act);
@@ -84,14 +86,14 @@ __global__ __launch_bounds__(256) void stem_bf16_kernel(const float* __restrict_
 
 // Round 3 form (as stem_fwd2_kernel in kd_conv.hip): the pixel's 9 * CIN inputs first, then one fma chain per output channel with
 // the weights as wave-uniform scalar loads (no LDS, no per-fma ds_read; the first form needed 256 VGPRs + 66 AGPRs at one wave/SIMD).
-template <int CIN>
+template <int CIN, int COUT>
 __global__ __launch_bounds__(256) void stem_bf16_v2_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ sc,
                                                            const float* __restrict__ sh, int act, bf16_t* __restrict__ y, int B, int H, int W,
                                                            int Ho, int Wo) {
   constexpr int KK = CIN * 9;
-  // a pixel = 64 contiguous output bytes per thread: through a wave-private LDS tile (rows padded to 80 bytes) so that the wave
-  // leaves four fully coalesced 1 KB stores instead of four stores that touch 64 lines each (as stem_fwd2_kernel)
-  constexpr int TLD = 40;                                                      // bf16 per tile row
+  // a pixel = 64 contiguous output bytes per thread (COUT = 32): through a wave-private LDS tile (rows padded by 16 bytes) so that
+  // the wave leaves COUT / 8 fully coalesced 1 KB stores instead of COUT / 8 stores that touch 64 lines each (as stem_fwd2_kernel)
+  constexpr int TLD = COUT + 8, Q = COUT / 8;                                  // bf16 per tile row, 16-byte pieces per pixel
   __shared__ __attribute__((aligned(16))) bf16_t tiles[4 * 64 * TLD];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   bf16_t* tile = tiles + wave * 64 * TLD;
@@ -117,7 +119,7 @@ __global__ __launch_bounds__(256) void stem_bf16_v2_kernel(const float* __restri
       }
     }
 #pragma unroll
-    for (int c = 0; c < 32; c += 8) {
+    for (int c = 0; c < COUT; c += 8) {
       float o[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -131,10 +133,10 @@ __global__ __launch_bounds__(256) void stem_bf16_v2_kernel(const float* __restri
     __builtin_amdgcn_wave_barrier();                            // (LDS is in-order per wave; this only pins the compiler's order)
     const int64_t wbase = base + wave * 64;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int pix = 16 * k + (lane >> 2), col = (lane & 3) * 8;
+    for (int k = 0; k < Q; ++k) {
+      const int i = 64 * k + lane, pix = i / Q, col = (i % Q) * 8;
       const u32x4 o = ld16(tile + pix * TLD + col);
-      if (wbase + pix < npix) st16(y + (wbase + pix) * 32 + col, o);
+      if (wbase + pix < npix) st16(y + (wbase + pix) * COUT + col, o);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -301,6 +303,10 @@ __global__ __launch_bounds__(256) void dw_bf16_s1_pipe_kernel(DwBfArgs a) {
 // esh[n]) (+ res[m][n]).  AIN 0: A bf16 [M][lda]; 1: A fp32 [M][lda] rounded to bf16 on load (LiDAR BEV grid);
 // 3: A = act0(bn0(layer0(point))) computed from the 16-byte point (LiDAR layer 0, K = 64).  EPI 0: bf16 store;
 // EPI 4: BEV scatter-max of the (non-negative) result into an fp32 grid by the unsigned bit pattern (cell index per row).
+// TAIL: K and N multiples of 8 only (the narrow layers of a lightweight TwinLite student, base_channels 8..40): the weight image
+// is zero-padded to Kp = K rounded up to 32 and to whole 32-column tiles, A fragments past K are zeros (never loaded), and the
+// columns past N of the last tile are neither read (bias / coefficients) nor stored.  Shapes that are multiples of 32 keep the
+// TAIL = false instances.
 struct GemmBfArgs {
   const void* A; int64_t lda;
   const float* W; const float* bias; const float* esc; const float* esh; int act;
@@ -319,13 +325,13 @@ __device__ __forceinline__ float xor1(float v) {
 
 constexpr int BF16_OCC = 2;           // first form: workgroups per CU (launch bounds and grid cap)
 constexpr int BF16_CH = 8;            // first form: k-steps (of 16) per register chunk
-template <int NB, int AIN, int EPI>
+template <int NB, int AIN, int EPI, bool TAIL = false>
 __global__ __launch_bounds__(64 * BW, BF16_OCC) void pw_gemm_bf16_kernel(GemmBfArgs g) {
   constexpr int N = 32 * NB, CH = BF16_CH;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int K = TAIL ? (g.K + 31) & ~31 : g.K, CPR = K / 8, NU = K / 16;   // K: the padded depth of the LDS weight image
   bf16_t* Wh = reinterpret_cast<bf16_t*>(smem_raw);                   // [N][K] bf16, 16-byte chunks swizzled
-  float* Co = reinterpret_cast<float*>(smem_raw + (size_t)N * g.K * 2);  // AIN 3: [7][K]
-  const int K = g.K, CPR = K / 8, NU = K / 16;
+  float* Co = reinterpret_cast<float*>(smem_raw + (size_t)N * K * 2);    // AIN 3: [7][K]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const bool odd = (lane & 1) != 0;
@@ -333,12 +339,17 @@ __global__ __launch_bounds__(64 * BW, BF16_OCC) void pw_gemm_bf16_kernel(GemmBfA
   auto swz = [&](int n) { return CPR % 16 == 0 ? (n & 15) : (CPR % 16 == 8 ? ((n >> 1) & 7) : ((n >> 2) & 3)); };
   for (int i = tid; i < N * K / 4; i += 64 * BW) {
     const int n = i / (K / 4), k4 = i % (K / 4);
-    const float4 w = kd_ld4(g.W + (int64_t)(n0 + n) * K + k4 * 4);
+    const bool in = !TAIL || (n0 + n < g.N && 4 * k4 < g.K);
+    const float4 w = in ? kd_ld4(g.W + (int64_t)(n0 + n) * g.K + k4 * 4) : kd_zero4();
     bf16_t* d = Wh + n * K + ((k4 >> 1) ^ swz(n)) * 8 + (k4 & 1) * 4;
     *reinterpret_cast<uint2*>(d) = make_uint2(pk_bf16(w.x, w.y), pk_bf16(w.z, w.w));
   }
   if (AIN == 3) {
     for (int k = tid; k < K; k += 64 * BW) {
+      if (TAIL && k >= g.K) {                                          // padded depth: layer-0 output 0 (zero weights behind it too)
+        for (int t = 0; t < 7; ++t) Co[t * K + k] = 0.f;
+        continue;
+      }
       Co[k] = g.sc0[k]; Co[K + k] = g.sh0[k];
       const float4 w0 = kd_ld4(g.l0w + k * 4);
       Co[2 * K + k] = w0.x; Co[3 * K + k] = w0.y; Co[4 * K + k] = w0.z; Co[5 * K + k] = w0.w;
@@ -357,13 +368,16 @@ __global__ __launch_bounds__(64 * BW, BF16_OCC) void pw_gemm_bf16_kernel(GemmBfA
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
     const int c = n0 + 32 * j + r;
-    bias[j] = g.bias ? g.bias[c] : 0.f;
-    esc[j] = g.esc[c]; esh[j] = g.esh[c];
+    const bool in = !TAIL || c < g.N;
+    bias[j] = g.bias && in ? g.bias[c] : 0.f;
+    esc[j] = in ? g.esc[c] : 0.f; esh[j] = in ? g.esh[c] : 0.f;
   }
 
   // A fragment of k-step u for this lane: 8 consecutive k of row r starting at 16 u + 8 h
   auto load_frag = [&](int64_t gm, int u) -> u32x4 {
-    if (AIN == 0) {
+    if (TAIL && 16 * u + 8 * h >= g.K) {                                 // K % 8 == 0: a fragment lies wholly inside or past K
+      return u32x4{0u, 0u, 0u, 0u};
+    } else if (AIN == 0) {
       return ld16(reinterpret_cast<const bf16_t*>(g.A) + gm * g.lda + 16 * u + 8 * h);
     } else if (AIN == 1) {
       const float* p = reinterpret_cast<const float*>(g.A) + gm * g.lda + 16 * u + 8 * h;
@@ -439,7 +453,7 @@ __global__ __launch_bounds__(64 * BW, BF16_OCC) void pw_gemm_bf16_kernel(GemmBfA
           float lo = odd ? x1 : v0, hi = odd ? v1 : x0;
           const int64_t row = m0 + rbase + 4 * h + (odd ? 1 : 0);
           const int col = n0 + 32 * j + (r & ~1);
-          if (row < M) {
+          if (row < M && (!TAIL || col < g.N)) {                        // (N even: col < N means col + 1 < N)
             if (g.res) {
               const uint32_t rr = *reinterpret_cast<const uint32_t*>(g.res + row * g.ldres + col);
               lo += bf_lo(rr); hi += bf_hi(rr);
@@ -468,7 +482,7 @@ __global__ __launch_bounds__(64 * BW, BF16_OCC) void pw_gemm_bf16_kernel(GemmBfA
             const bool first = i == 0 || cellv[i] != cellv[i > 0 ? i - 1 : 0];
             const bool last = i == 3 || cellv[i] != cellv[i < 3 ? i + 1 : i];
             run = (first || v > run) ? v : run;
-            if (last && cellv[i] >= 0 && run > 0.f)
+            if (last && cellv[i] >= 0 && run > 0.f && (!TAIL || n0 + 32 * j + r < g.N))
               atomicMax(reinterpret_cast<unsigned*>(g.grid + (int64_t)cellv[i] * g.ldgrid + n0 + 32 * j + r), __float_as_uint(run));
           }
         }
@@ -755,24 +769,35 @@ __global__ __launch_bounds__(256) void weighted_tail_bf16_kernel(const bf16_t* _
   }
 }
 
-template <int NB>
+template <int NB, bool TAIL = false>
 int launch_gemm_bf16(GemmBfArgs& g, int ain, int epi, hipStream_t st) {
-  const int ntiles = g.N / (32 * NB);
+  const int ntiles = (g.N + 32 * NB - 1) / (32 * NB);
+  const int Kp = TAIL ? (g.K + 31) & ~31 : g.K;
   int64_t want = (g.M + 32 * BW - 1) / (32 * BW);
   int cap = 128 * BF16_OCC / ntiles; if (cap < 1) cap = 1;
   const dim3 grid((unsigned)(want < cap ? want : cap), ntiles);
-  const size_t lds = (size_t)32 * NB * g.K * 2 + (ain == 3 ? (size_t)7 * g.K * 4 : 0);
+  const size_t lds = (size_t)32 * NB * Kp * 2 + (ain == 3 ? (size_t)7 * Kp * 4 : 0);
 #define KD_BCASE(A_, E_)                                                                                               \
   if (ain == A_ && epi == E_) {                                                                                        \
-    const hipError_t le = hipFuncSetAttribute((const void*)pw_gemm_bf16_kernel<NB, A_, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+    const hipError_t le = hipFuncSetAttribute((const void*)pw_gemm_bf16_kernel<NB, A_, E_, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     KD_REQUIRE(le == hipSuccess, (int)le, "kd_bf16_pwconv: cannot raise the dynamic LDS limit to %zu B: %s", lds, hipGetErrorString(le)); \
-    hipLaunchKernelGGL((pw_gemm_bf16_kernel<NB, A_, E_>), grid, dim3(64 * BW), lds, st, g);                            \
+    hipLaunchKernelGGL((pw_gemm_bf16_kernel<NB, A_, E_, TAIL>), grid, dim3(64 * BW), lds, st, g);                      \
     return kd_check_launch("kd_bf16_pwconv");                                                                          \
   }
   KD_BCASE(0, 0) KD_BCASE(1, 0) KD_BCASE(3, 0) KD_BCASE(0, 4)
 #undef KD_BCASE
   kd_set_error("kd_bf16_pwconv: unsupported (input kind %d, epilogue %d)", ain, epi);
   return KD_ERR_ARG;
+}
+
+template <int COUT>
+int stem_bf16_launch(const float* x, const float* w, const float* sc, const float* sh, int act, void* y, int B, int Cin, int H, int W, int Ho,
+                     int Wo, int grid, hipStream_t st) {
+  if (Cin == 3) hipLaunchKernelGGL((stem_bf16_v2_kernel<3, COUT>), dim3((unsigned)grid), dim3(256), 0, st, x, w, sc, sh, act, (bf16_t*)y, B, H, W,
+                                   Ho, Wo);
+  else hipLaunchKernelGGL((stem_bf16_kernel<COUT>), dim3((unsigned)grid), dim3(256), (size_t)Cin * 9 * COUT * sizeof(float), st, x, w, sc, sh, act,
+                          (bf16_t*)y, B, Cin, H, W, Ho, Wo);
+  return kd_check_launch("kd_bf16_stem");
 }
 
 constexpr int KD_BF16_V2_NO_INSTANCE = -12345;
@@ -831,16 +856,19 @@ extern "C" {
 
 int kd_bf16_stem(const float* x_nchw, const float* w, const float* sc, const float* sh, int act, void* y, int B, int Cin, int H,
                  int W, int Cout, void* stream) {
-  KD_REQUIRE(x_nchw && w && sc && sh && y && B > 0 && Cout == 32 && Cin >= 1 && Cin <= 4, KD_ERR_ARG, "kd_bf16_stem: bad args");
+  KD_REQUIRE(x_nchw && w && sc && sh && y && B > 0 && Cin >= 1 && Cin <= 4, KD_ERR_ARG, "kd_bf16_stem: bad args");
+  KD_REQUIRE(kd_stem_width_ok(Cout), KD_ERR_SHAPE, "kd_bf16_stem: only Cout in {8, 16, 24, 32, 40} (got %d)", Cout);
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t npix = (int64_t)B * Ho * Wo;
   int64_t grid = (npix + 255) / 256;
   if (grid > 4096) grid = 4096;
-  if (Cin == 3) hipLaunchKernelGGL(stem_bf16_v2_kernel<3>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x_nchw, w, sc, sh, act,
-                                   (bf16_t*)y, B, H, W, Ho, Wo);
-  else hipLaunchKernelGGL(stem_bf16_kernel, dim3((unsigned)grid), dim3(256), (size_t)Cin * 9 * 32 * sizeof(float), (hipStream_t)stream, x_nchw, w, sc,
-                          sh, act, (bf16_t*)y, B, Cin, H, W, Ho, Wo);
-  return kd_check_launch("kd_bf16_stem");
+  switch (Cout) {
+    case 8: return stem_bf16_launch<8>(x_nchw, w, sc, sh, act, y, B, Cin, H, W, Ho, Wo, (int)grid, (hipStream_t)stream);
+    case 16: return stem_bf16_launch<16>(x_nchw, w, sc, sh, act, y, B, Cin, H, W, Ho, Wo, (int)grid, (hipStream_t)stream);
+    case 24: return stem_bf16_launch<24>(x_nchw, w, sc, sh, act, y, B, Cin, H, W, Ho, Wo, (int)grid, (hipStream_t)stream);
+    case 40: return stem_bf16_launch<40>(x_nchw, w, sc, sh, act, y, B, Cin, H, W, Ho, Wo, (int)grid, (hipStream_t)stream);
+    default: return stem_bf16_launch<32>(x_nchw, w, sc, sh, act, y, B, Cin, H, W, Ho, Wo, (int)grid, (hipStream_t)stream);
+  }
 }
 
 int kd_bf16_dwconv3x3(const void* x, const float* w, const float* sc, const float* sh, int act, void* y, int B, int H, int W,
@@ -872,8 +900,8 @@ int kd_bf16_pwconv(const void* A, int64_t lda, int a_kind, const float* W, const
                    int act, void* C, int64_t ldc, const void* res, int64_t ldres, int epi, int64_t M, int K, int N,
                    const int* m_dev, const float* l0w, const float* l0b, const float* sc0, const float* sh0, int act0,
                    const int* cell, float* grid, int64_t ldgrid, void* stream) {
-  KD_REQUIRE(A && W && esc && esh && M > 0 && K >= 16 && N >= 32, KD_ERR_ARG, "kd_bf16_pwconv: bad args");
-  KD_REQUIRE(K % 32 == 0 && (K / 8) % 4 == 0 && N % 32 == 0 && K <= 1024, KD_ERR_SHAPE, "kd_bf16_pwconv: K=%d must be a multiple of 32, N=%d of 32", K, N);
+  KD_REQUIRE(A && W && esc && esh && M > 0 && K >= 8 && N >= 8, KD_ERR_ARG, "kd_bf16_pwconv: bad args");
+  KD_REQUIRE(K % 8 == 0 && N % 8 == 0 && K <= 1024, KD_ERR_SHAPE, "kd_bf16_pwconv: K=%d and N=%d must be multiples of 8, K <= 1024", K, N);
   KD_REQUIRE(a_kind == 3 || (lda % (a_kind == 0 ? 8 : 4) == 0 && kd_aligned16(A)), KD_ERR_ALIGN, "kd_bf16_pwconv: A alignment");
   KD_REQUIRE(epi == 4 ? (cell && grid && (act == KD_ACT_RELU || act == KD_ACT_RELU6)) : (C != nullptr && ldc % 2 == 0 && (!res || ldres % 2 == 0)), KD_ERR_ARG,
              "kd_bf16_pwconv: epilogue arguments");
@@ -881,6 +909,7 @@ int kd_bf16_pwconv(const void* A, int64_t lda, int a_kind, const float* W, const
   GemmBfArgs g{A, lda, W, bias, esc, esh, act, (bf16_t*)C, ldc, (const bf16_t*)res, ldres, M, K, N, m_dev, l0w, l0b, sc0, sh0, act0,
                cell, grid, ldgrid};
   hipStream_t st = (hipStream_t)stream;
+  if (K % 32 != 0 || N % 32 != 0) return launch_gemm_bf16<1, true>(g, a_kind, epi, st);     // narrow shapes: padded, masked tile
   if (a_kind == 0 && epi == 0 && !m_dev) {
     const int rc = launch_gemm_bf16_v2(g, st);
     if (rc != KD_BF16_V2_NO_INSTANCE) return rc;

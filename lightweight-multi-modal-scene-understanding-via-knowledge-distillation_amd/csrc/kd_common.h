@@ -55,6 +55,9 @@ static inline hipError_t kd_raise_dynamic_lds(const void* fn, size_t bytes, std:
 
 static inline bool kd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// stem output widths with a kernel instance (TwinLiteEncoder base_channels: multiples of 8 up to 40)
+static inline bool kd_stem_width_ok(int cout) { return cout % 8 == 0 && cout >= 8 && cout <= 40; }
+
 // z = raw*scale + shift, as ONE fused multiply-add: forward, backward masks and the scatter-max
 // tie test all call this, so a recomputed value is bit-identical to the one used in the forward.
 __device__ __forceinline__ float kd_affine(float raw, float sc, float sh) { return fmaf(raw, sc, sh); }

@@ -11,24 +11,26 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// stem: y[b,ho,wo,co] = sum_{ci,kh,kw} x[b,ci,2ho-1+kh,2wo-1+kw] * w[co,ci,kh,kw], Cout == 32.
-// One thread = one output pixel x 32 channels (writes 128 contiguous bytes); weights in LDS.
+// stem: y[b,ho,wo,co] = sum_{ci,kh,kw} x[b,ci,2ho-1+kh,2wo-1+kw] * w[co,ci,kh,kw], Cout == COUT (8, 16, 24, 32 or 40).
+// One thread = one output pixel x COUT channels (writes 4 * COUT contiguous bytes); weights in LDS.
+template <int COUT>
 __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        float* __restrict__ y, float* __restrict__ partial, int B,
                                                        int Cin, int H, int W, int Ho, int Wo) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int RLD = COUT + 1;
   const int KK = Cin * 9;
-  float* ws = sm;                      // [KK][32]  (transposed: tap-major so a tap's 32 weights are contiguous)
-  float* red = sm + KK * 32;           // [256][33] stats staging
-  for (int i = threadIdx.x; i < KK * 32; i += 256) ws[(i % KK) * 32 + i / KK] = w[i];
+  float* ws = sm;                      // [KK][COUT]  (transposed: tap-major so a tap's COUT weights are contiguous)
+  float* red = sm + KK * COUT;         // [256][COUT + 1] stats staging
+  for (int i = threadIdx.x; i < KK * COUT; i += 256) ws[(i % KK) * COUT + i / KK] = w[i];
   __syncthreads();
   const int64_t npix = (int64_t)B * Ho * Wo;
   float s1 = 0.f, s2 = 0.f;            // this thread's (stat, channel) column sum, see below
   for (int64_t base = (int64_t)blockIdx.x * 256; base < npix; base += (int64_t)gridDim.x * 256) {
     const int64_t p = base + threadIdx.x;
-    float acc[32];
+    float acc[COUT];
 #pragma unroll
-    for (int c = 0; c < 32; ++c) acc[c] = 0.f;
+    for (int c = 0; c < COUT; ++c) acc[c] = 0.f;
     if (p < npix) {
       const int wo = (int)(p % Wo), ho = (int)((p / Wo) % Ho), b = (int)(p / ((int64_t)Wo * Ho));
       for (int ci = 0; ci < Cin; ++ci) {
@@ -41,35 +43,35 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
             const int wi = 2 * wo - 1 + kw;
             float v = 0.f;
             if (hi >= 0 && hi < H && wi >= 0 && wi < W) v = xp[(int64_t)hi * W + wi];
-            const float* wt = ws + (ci * 9 + kh * 3 + kw) * 32;
+            const float* wt = ws + (ci * 9 + kh * 3 + kw) * COUT;
 #pragma unroll
-            for (int c = 0; c < 32; ++c) acc[c] = fmaf(v, wt[c], acc[c]);
+            for (int c = 0; c < COUT; ++c) acc[c] = fmaf(v, wt[c], acc[c]);
           }
         }
       }
-      float* yp = y + p * 32;
+      float* yp = y + p * COUT;
 #pragma unroll
-      for (int c = 0; c < 32; c += 4) kd_st4(yp + c, make_float4(acc[c], acc[c + 1], acc[c + 2], acc[c + 3]));
+      for (int c = 0; c < COUT; c += 4) kd_st4(yp + c, make_float4(acc[c], acc[c + 1], acc[c + 2], acc[c + 3]));
     }
     if (partial) {
       __syncthreads();
 #pragma unroll
-      for (int c = 0; c < 32; ++c) red[threadIdx.x * 33 + c] = acc[c];   // rows past npix hold zeros
+      for (int c = 0; c < COUT; ++c) red[threadIdx.x * RLD + c] = acc[c];   // rows past npix hold zeros
       __syncthreads();
-      if (threadIdx.x < 64) {
-        const int c = threadIdx.x & 31, st = threadIdx.x >> 5;
+      if (threadIdx.x < 2 * COUT) {
+        const int c = threadIdx.x % COUT, st = threadIdx.x / COUT;
         float s = 0.f;
         for (int r = 0; r < 256; ++r) {
-          const float v = red[r * 33 + c];
+          const float v = red[r * RLD + c];
           s += st ? v * v : v;
         }
         if (st) s2 += s; else s1 += s;
       }
     }
   }
-  if (partial && threadIdx.x < 64) {
-    const int c = threadIdx.x & 31, st = threadIdx.x >> 5;
-    partial[((int64_t)blockIdx.x * 2 + st) * 32 + c] = st ? s2 : s1;
+  if (partial && threadIdx.x < 2 * COUT) {
+    const int c = threadIdx.x % COUT, st = threadIdx.x / COUT;
+    partial[((int64_t)blockIdx.x * 2 + st) * COUT + c] = st ? s2 : s1;
   }
 }
 
@@ -81,25 +83,29 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
 // FIN (round 4, inference: eval mode without autograd -- the frozen KD teacher, validation): the stem's BatchNorm + activation
 // finish, act(fma(raw, sc[c], sh[c])), applied here instead of by a kd_bn_act_apply pass over the [B, 32, H/2, W/2] map (the same
 // operations in the same order: identical bits; 0.23 ms per step at 256 frames).  sc / sh are wave-uniform scalar loads.
-template <int CIN, bool STATS, bool FIN = false>
+// COUT (8, 16, 24, 32 or 40): the stem width, TwinLiteEncoder's base_channels.  Every COUT runs the same per-channel fma chain
+// and the same statistics order; COUT = 32 is the network's own width and the shape the comments below measure.
+template <int CIN, int COUT, bool STATS, bool FIN = false>
 __global__ __launch_bounds__(256) void stem_fwd2_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         float* __restrict__ y, float* __restrict__ partial, int B, int H, int W,
                                                         int Ho, int Wo, const float* __restrict__ fsc = nullptr,
                                                         const float* __restrict__ fsh = nullptr, int fact = 0) {
+  static_assert(COUT % 4 == 0 && COUT >= 8 && COUT <= 40, "stem width");
   constexpr int KK = CIN * 9;
-  // A thread owns one pixel = 128 contiguous output bytes; stored straight from its registers that is eight 16-byte stores whose
-  // 64 lanes hit 64 different lines each (probe: 357 us with the stores, 72 us without: 1.9 TB/s).  So a wave's 64 x 32 results
-  // go through a wave-private LDS tile (rows padded to 36 floats: aligned 16-byte accesses in both directions) and leave as eight
-  // fully coalesced 1 KB stores: lane l writes bytes [16 l, 16 l + 16) of each KB.  The tile doubles as the statistics staging.
-  constexpr int TLD = 36;
+  // A thread owns one pixel = 128 contiguous output bytes (COUT = 32); stored straight from its registers that is eight 16-byte
+  // stores whose 64 lanes hit 64 different lines each (probe: 357 us with the stores, 72 us without: 1.9 TB/s).  So a wave's
+  // 64 x COUT results go through a wave-private LDS tile (rows padded to COUT + 4 floats: aligned 16-byte accesses in both
+  // directions) and leave as COUT / 4 fully coalesced 1 KB stores: lane l writes bytes [16 l, 16 l + 16) of each KB.  The tile
+  // doubles as the statistics staging.
+  constexpr int TLD = COUT + 4, RLD = COUT + 1, Q = COUT / 4;     // Q: 16-byte pieces per pixel
   __shared__ __attribute__((aligned(16))) float red[4 * 64 * TLD];
-  static_assert(4 * 64 * TLD >= 256 * 33, "the end-of-kernel statistics reduction reuses the tile");
+  static_assert(4 * 64 * TLD >= 256 * RLD, "the end-of-kernel statistics reduction reuses the tile");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* tile = red + wave * 64 * TLD;
   const int64_t npix = (int64_t)B * Ho * Wo;
-  float s1[STATS ? 32 : 1], s2[STATS ? 32 : 1];
+  float s1[STATS ? COUT : 1], s2[STATS ? COUT : 1];
 #pragma unroll
-  for (int c = 0; c < (STATS ? 32 : 1); ++c) { s1[c] = 0.f; s2[c] = 0.f; }
+  for (int c = 0; c < (STATS ? COUT : 1); ++c) { s1[c] = 0.f; s2[c] = 0.f; }
   for (int64_t base = (int64_t)blockIdx.x * 256; base < npix; base += (int64_t)gridDim.x * 256) {
     const int64_t p_raw = base + threadIdx.x;
     const bool pok = p_raw < npix;
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(256) void stem_fwd2_kernel(const float* __restrict_
         }
       }
 #pragma unroll
-      for (int c4 = 0; c4 < 32; c4 += 4) {
+      for (int c4 = 0; c4 < COUT; c4 += 4) {
         float a[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -139,31 +145,42 @@ __global__ __launch_bounds__(256) void stem_fwd2_kernel(const float* __restrict_
     __builtin_amdgcn_wave_barrier();                            // (LDS is in-order per wave; this only pins the compiler's order)
     const int64_t wbase = base + wave * 64;                     // first pixel of this wave's 64
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int pix = 8 * k + (lane >> 3), col = (lane & 7) * 4;
+    for (int k = 0; k < Q; ++k) {
+      const int i = 64 * k + lane, pix = i / Q, col = (i % Q) * 4;
       const float4 o = kd_ld4(tile + pix * TLD + col);
-      if (wbase + pix < npix) kd_st4(y + (wbase + pix) * 32 + col, o);
+      if (wbase + pix < npix) kd_st4(y + (wbase + pix) * COUT + col, o);
     }
     __builtin_amdgcn_wave_barrier();
   }
   if (STATS) {
+    // per (stat, channel): 8 segments of 32 threads' sums, then the 8 segment sums in order
+    constexpr int NI = (8 * COUT + 255) / 256;                  // (segment, channel) items per thread
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
       __syncthreads();
 #pragma unroll
-      for (int c = 0; c < 32; ++c) red[threadIdx.x * 33 + c] = st ? s2[c] : s1[c];
+      for (int c = 0; c < COUT; ++c) red[threadIdx.x * RLD + c] = st ? s2[c] : s1[c];
       __syncthreads();
-      const int c = threadIdx.x & 31, seg = threadIdx.x >> 5;            // 8 segments of 32 threads' sums per channel
-      float s = 0.f;
-      for (int r = 0; r < 32; ++r) s += red[(seg * 32 + r) * 33 + c];
+      float s[NI];
+#pragma unroll
+      for (int n = 0; n < NI; ++n) {
+        const int it = threadIdx.x + 256 * n, c = it % COUT, seg = it / COUT;
+        s[n] = 0.f;
+        if (it < 8 * COUT)
+          for (int r = 0; r < 32; ++r) s[n] += red[(seg * 32 + r) * RLD + c];
+      }
       __syncthreads();
-      red[seg * 33 + c] = s;
+#pragma unroll
+      for (int n = 0; n < NI; ++n) {
+        const int it = threadIdx.x + 256 * n;
+        if (it < 8 * COUT) red[(it / COUT) * RLD + it % COUT] = s[n];
+      }
       __syncthreads();
-      if (threadIdx.x < 32) {
+      if (threadIdx.x < COUT) {
         float tot = 0.f;
 #pragma unroll
-        for (int g8 = 0; g8 < 8; ++g8) tot += red[g8 * 33 + threadIdx.x];
-        partial[((int64_t)blockIdx.x * 2 + st) * 32 + threadIdx.x] = tot;
+        for (int g8 = 0; g8 < 8; ++g8) tot += red[g8 * RLD + threadIdx.x];
+        partial[((int64_t)blockIdx.x * 2 + st) * COUT + threadIdx.x] = tot;
       }
     }
   }
@@ -1169,6 +1186,26 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_sw_kernel(DwBwdArgs a) {
   }
 }
 
+template <int COUT>
+int stem_fwd_launch(const float* x, const float* w, float* y, float* partial, int B, int Cin, int H, int W, int Ho, int Wo, int grid,
+                    hipStream_t st) {
+  if (Cin == 3) {
+    if (partial) hipLaunchKernelGGL((stem_fwd2_kernel<3, COUT, true>), dim3(grid), dim3(256), 0, st, x, w, y, partial, B, H, W, Ho, Wo);
+    else hipLaunchKernelGGL((stem_fwd2_kernel<3, COUT, false>), dim3(grid), dim3(256), 0, st, x, w, y, partial, B, H, W, Ho, Wo);
+    return kd_check_launch("kd_stem_conv_fwd");
+  }
+  const size_t shm = (size_t)(Cin * 9 * COUT + 256 * (COUT + 1)) * sizeof(float);
+  hipLaunchKernelGGL((stem_fwd_kernel<COUT>), dim3(grid), dim3(256), shm, st, x, w, y, partial, B, Cin, H, W, Ho, Wo);
+  return kd_check_launch("kd_stem_conv_fwd");
+}
+
+template <int COUT>
+int stem_infer_launch(const float* x, const float* w, const float* sc, const float* sh, int act, float* y, int B, int H, int W, int Ho,
+                      int Wo, int grid, hipStream_t st) {
+  hipLaunchKernelGGL((stem_fwd2_kernel<3, COUT, false, true>), dim3(grid), dim3(256), 0, st, x, w, y, nullptr, B, H, W, Ho, Wo, sc, sh, act);
+  return kd_check_launch("kd_stem_conv_fwd_infer");
+}
+
 }  // namespace
 
 // stride-1 backward form: 0 separate data / weight kernels, 1 fused column walk, 2 fused tile form, 3 (default) by shape
@@ -1208,32 +1245,34 @@ int64_t kd_stem_stat_rows(int64_t npix) {
 int kd_stem_conv_fwd(const float* x_nchw, const float* w, float* y_nhwc, float* partial, int B, int Cin, int H, int W,
                      int Cout, void* stream) {
   KD_REQUIRE(x_nchw && w && y_nhwc && B > 0 && H > 0 && W > 0, KD_ERR_ARG, "kd_stem_conv_fwd: bad args");
-  KD_REQUIRE(Cout == 32 && Cin >= 1 && Cin <= 4, KD_ERR_SHAPE, "kd_stem_conv_fwd: only Cout=32, Cin<=4 (got %d,%d)", Cout, Cin);
+  KD_REQUIRE(kd_stem_width_ok(Cout) && Cin >= 1 && Cin <= 4, KD_ERR_SHAPE,
+             "kd_stem_conv_fwd: only Cout in {8, 16, 24, 32, 40}, Cin<=4 (got %d,%d)", Cout, Cin);
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  const int64_t npix = (int64_t)B * Ho * Wo;
-  const int grid = (int)kd_stem_stat_rows(npix);
-  hipStream_t st = (hipStream_t)stream;
-  if (Cin == 3) {
-    if (partial) hipLaunchKernelGGL((stem_fwd2_kernel<3, true>), dim3(grid), dim3(256), 0, st, x_nchw, w, y_nhwc, partial, B, H, W, Ho, Wo);
-    else hipLaunchKernelGGL((stem_fwd2_kernel<3, false>), dim3(grid), dim3(256), 0, st, x_nchw, w, y_nhwc, partial, B, H, W, Ho, Wo);
-    return kd_check_launch("kd_stem_conv_fwd");
+  const int grid = (int)kd_stem_stat_rows((int64_t)B * Ho * Wo);
+  switch (Cout) {
+    case 8: return stem_fwd_launch<8>(x_nchw, w, y_nhwc, partial, B, Cin, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    case 16: return stem_fwd_launch<16>(x_nchw, w, y_nhwc, partial, B, Cin, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    case 24: return stem_fwd_launch<24>(x_nchw, w, y_nhwc, partial, B, Cin, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    case 40: return stem_fwd_launch<40>(x_nchw, w, y_nhwc, partial, B, Cin, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    default: return stem_fwd_launch<32>(x_nchw, w, y_nhwc, partial, B, Cin, H, W, Ho, Wo, grid, (hipStream_t)stream);
   }
-  const size_t shm = (size_t)(Cin * 9 * 32 + 256 * 33) * sizeof(float);
-  hipLaunchKernelGGL(stem_fwd_kernel, dim3(grid), dim3(256), shm, st, x_nchw, w, y_nhwc, partial, B,
-                     Cin, H, W, Ho, Wo);
-  return kd_check_launch("kd_stem_conv_fwd");
 }
 
 // inference: y = act(bn(conv(x))) in one kernel (eval-mode coefficients sc / sh of the stem's BatchNorm)
 int kd_stem_conv_fwd_infer(const float* x_nchw, const float* w, const float* sc, const float* sh, int act, float* y_nhwc, int B,
                            int Cin, int H, int W, int Cout, void* stream) {
   KD_REQUIRE(x_nchw && w && sc && sh && y_nhwc && B > 0 && H > 0 && W > 0, KD_ERR_ARG, "kd_stem_conv_fwd_infer: bad args");
-  KD_REQUIRE(Cout == 32 && Cin == 3, KD_ERR_SHAPE, "kd_stem_conv_fwd_infer: only Cout=32, Cin=3 (got %d,%d)", Cout, Cin);
+  KD_REQUIRE(kd_stem_width_ok(Cout) && Cin == 3, KD_ERR_SHAPE, "kd_stem_conv_fwd_infer: only Cout in {8, 16, 24, 32, 40}, Cin=3 (got %d,%d)",
+             Cout, Cin);
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int grid = (int)kd_stem_stat_rows((int64_t)B * Ho * Wo);
-  hipLaunchKernelGGL((stem_fwd2_kernel<3, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x_nchw, w, y_nhwc, nullptr, B, H, W,
-                     Ho, Wo, sc, sh, act);
-  return kd_check_launch("kd_stem_conv_fwd_infer");
+  switch (Cout) {
+    case 8: return stem_infer_launch<8>(x_nchw, w, sc, sh, act, y_nhwc, B, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    case 16: return stem_infer_launch<16>(x_nchw, w, sc, sh, act, y_nhwc, B, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    case 24: return stem_infer_launch<24>(x_nchw, w, sc, sh, act, y_nhwc, B, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    case 40: return stem_infer_launch<40>(x_nchw, w, sc, sh, act, y_nhwc, B, H, W, Ho, Wo, grid, (hipStream_t)stream);
+    default: return stem_infer_launch<32>(x_nchw, w, sc, sh, act, y_nhwc, B, H, W, Ho, Wo, grid, (hipStream_t)stream);
+  }
 }
 
 int kd_stem_im2col(const float* x_nchw, float* col, int B, int Cin, int H, int W, int Kp, void* stream) {

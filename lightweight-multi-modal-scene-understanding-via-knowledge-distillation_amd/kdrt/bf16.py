@@ -99,12 +99,14 @@ def forward_bf16(model, images: torch.Tensor, points: torch.Tensor, return_inter
     dev = img.device
     # ---- camera encoder (camera_encoder.py:63-115) ------------------------------------------------------------------------
     stem = units.UnitSpec("stem", enc.stem[0], enc.stem[1], ACT_RELU6)
+    Cs = enc.stem[0].weight.shape[0]                    # the encoder width, base_channels
+    units.check_encoder_width(Cs)
     bnc = _coef(stem)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    x = torch.empty(B * Ho * Wo, 32, device=dev, dtype=torch.bfloat16)
+    x = torch.empty(B * Ho * Wo, Cs, device=dev, dtype=torch.bfloat16)
     e0 = ops._prof_begin()
-    lib.call("kd_bf16_stem", P(img), P(enc.stem[0].weight), P(bnc.scale), P(bnc.shift), ACT_RELU6, P(x), B, Cin, H, W, 32, stream())
-    ops._prof_end(e0, "bf16_stem", 2.0 * B * Ho * Wo * 32 * Cin * 9, 4.0 * B * Cin * H * W + 2.0 * B * Ho * Wo * 32)
+    lib.call("kd_bf16_stem", P(img), P(enc.stem[0].weight), P(bnc.scale), P(bnc.shift), ACT_RELU6, P(x), B, Cin, H, W, Cs, stream())
+    ops._prof_end(e0, "bf16_stem", 2.0 * B * Ho * Wo * Cs * Cin * 9, 4.0 * B * Cin * H * W + 2.0 * B * Ho * Wo * Cs)
     geom = (B, Ho, Wo)
     feats = {}
     for name in ("stage1", "stage2", "stage3", "stage4", "stage5"):

@@ -20,6 +20,19 @@ from .lib import KDError, lib
 from .ops import ACT_NONE, ACT_RELU, BNC, Operand, P, ld, stream
 
 
+# TwinLiteEncoder widths (base_channels) the kernels have instances for: the stem kernels are instantiated for these output
+# widths, and 40 is the cap because stage 5's hidden width, 24 * base_channels, must stay within the depthwise kernels' C <= 1024.
+ENCODER_WIDTHS = (8, 16, 24, 32, 40)
+
+
+def check_encoder_width(base_channels: int) -> None:
+    """Raise KDError unless a TwinLiteEncoder of this width can run on the kernels (called on the first GPU forward, so that
+    building a model and loading a state dict stay possible at any width)."""
+    if base_channels not in ENCODER_WIDTHS:
+        raise KDError(f"TwinLiteEncoder(base_channels={base_channels}) is not supported: base_channels must be one of "
+                      f"{', '.join(map(str, ENCODER_WIDTHS))} (a multiple of 8, at most 40)")
+
+
 class UnitSpec:
     """kind: 'pw' (1x1 conv / Conv1d k=1), 'dw' (depthwise 3x3), 'stem' (3x3 s2 dense), 'l0' (LiDAR 4->C),
     'ct' (ConvTranspose2d k=4 s=2 p=1, bias-free: GEMM to [M_in, Cout*16] columns + col2im)."""

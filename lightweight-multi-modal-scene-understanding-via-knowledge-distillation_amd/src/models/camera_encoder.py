@@ -74,6 +74,7 @@ class TwinLiteEncoder(nn.Module):
         """`_skip_stages` (not in the reference's signature; keyword-only use by CompleteSegmentationModel): multiscale maps the
         CALLER promises not to read -- they are left out of the returned dict.  Without it the key set is the reference's,
         {stage2, stage3, stage4, stage5}, in train() and eval() alike."""
+        U.check_encoder_width(self.stem[0].out_channels)
         stem = U.UnitSpec("stem", self.stem[0], self.stem[1], ACT_RELU6)
         # Training: a block that feeds ONLY the residual block after it hands its output over un-materialised (PairChainFn):
         # the stem -> stage1 always; stage2 -> stage3 unless somebody reads stage2's map (the owning model says per call which

@@ -4,6 +4,8 @@ point as the reference's train_with_fusion_ablation.py, running on the MI355X-na
 Environment knobs (defaults reproduce the reference's literals, train_with_fusion_ablation.py:17-61):
   KD_DATA_ROOT   PandaSet root (reference: a hard-coded Windows path)
   KD_TEACHER     optional checkpoint of a concat-fusion teacher: switches every variant to KD training
+  KD_STUDENT_BASE_CHANNELS   with KD_TEACHER: the student's TwinLiteEncoder width, one of 8 16 24 32 40 (default 32, the
+                 teacher's); the teacher is always built at 32 to load its checkpoint
   KD_EPOCHS / KD_BATCH_SIZE   20 / 4
 Launch with `python -m torch.distributed.run --nproc-per-node N` for data-parallel training: one process per GPU,
 frames sharded over ranks in equal counts (every rank runs the same number of steps), rank 0's initial weights
@@ -31,8 +33,8 @@ def log(*a, **k):
         print(*a, **k)
 
 
-def build_model(fusion_type, fusion_out_channels, device, num_classes=2):
-    cam_enc = TwinLiteEncoder(return_multiscale=True)
+def build_model(fusion_type, fusion_out_channels, device, num_classes=2, base_channels=32):
+    cam_enc = TwinLiteEncoder(base_channels=base_channels, return_multiscale=True)
     lidar_enc = LiDAREncoder(encoder_type="spatial", grid_size=(64, 64), use_vectorized=True)
     return CompleteSegmentationModel(camera_encoder=cam_enc, lidar_encoder=lidar_enc, num_classes=num_classes,
                                      fusion_type=fusion_type, fusion_out_channels=fusion_out_channels,
@@ -45,12 +47,15 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
     train_loader, val_loader = create_pandaset_dataloaders(
         root=root, train_scenes=train_scenes, val_scenes=val_scenes,
         batch_size=int(os.environ.get("KD_BATCH_SIZE", 4)), num_workers=2, verbose=False)
-    model = build_model(fusion_type, fusion_out_channels, device)
+    teacher_ckpt = os.environ.get("KD_TEACHER")
+    base = int(os.environ.get("KD_STUDENT_BASE_CHANNELS", 32)) if teacher_ckpt else 32
+    model = build_model(fusion_type, fusion_out_channels, device, base_channels=base)
     summary = model.get_architecture_summary()
     log(f"\nModel: {fusion_type}\n  Total params: {summary['total_params']}\n  Fusion params: {summary['fusion_params']}")
+    if base != 32:
+        log(f"  Student camera encoder: base_channels={base}, {summary['camera_params']} params")
     kw = dict(lr=1e-3, weight_decay=1e-3, save_dir=f"checkpoints/fusion_ablation_{fusion_type}",
               class_weights=[0.4, 3.5], num_epochs=int(os.environ.get("KD_EPOCHS", 20)))
-    teacher_ckpt = os.environ.get("KD_TEACHER")
     if teacher_ckpt:
         teacher = build_model("concat", 256, device)
         teacher.load_state_dict(torch.load(teacher_ckpt, map_location=device)["model_state"])
