@@ -364,8 +364,11 @@ int64_t kd_mse_slab_blocks(int64_t n);
 int kd_mse_partial(const float* a, const float* b, int64_t n, float gcoef, float* da, float* slab, void* stream);
 int kd_kd_objective_final(const float* ce_kl, const float* slab_c, int64_t n_c, const float* slab_l, int64_t n_l, float ckl, float beta,
                           float* out, void* stream);
+/* pred[B*HW] = argmax over the NC (1..4) classes, first maximum wins; conf[M*M] (ACCUMULATED into) counts a pixel at [t, argmax]
+ * when t != ignore_index and 0 <= t < M and argmax < M: M (1..4) is the width of the matrix, independent of NC.  Either of conf
+ * and pred may be NULL; target NULL: no counting. */
 int kd_argmax_confusion(const float* logits, const int64_t* target, int ignore_index, uint64_t* conf,
-                        int64_t* pred, int B, int NC, int HW, void* stream);
+                        int64_t* pred, int B, int NC, int M, int HW, void* stream);
 int kd_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int step, float ginv, void* stream);
 /* hipGraph-replay-safe form: state = device float[4] {lr, step, 1-beta1^step, sqrt(1-beta2^step)}; the call

@@ -176,7 +176,7 @@ __global__ void mse_final_kernel(const float* slab, int nblk, double n, float* l
 }
 
 __global__ __launch_bounds__(256) void confusion_kernel(const float* z, const int64_t* target, int ignore_index,
-                                                        int64_t npix, int HW, int NC, unsigned long long* conf,
+                                                        int64_t npix, int HW, int NC, int M, unsigned long long* conf,
                                                         int64_t* pred) {
   __shared__ unsigned int loc[MAXC * MAXC];
   if (threadIdx.x < MAXC * MAXC) loc[threadIdx.x] = 0;
@@ -191,10 +191,10 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* z, const in
     }
     if (pred) pred[i] = best;
     const int64_t t = target ? target[i] : ignore_index;
-    if (target && t != ignore_index && t >= 0 && t < NC) atomicAdd(&loc[t * NC + best], 1u);
+    if (target && t != ignore_index && t >= 0 && t < M && best < M) atomicAdd(&loc[t * M + best], 1u);
   }
   __syncthreads();
-  if (conf && threadIdx.x < NC * NC && loc[threadIdx.x]) atomicAdd(&conf[threadIdx.x], (unsigned long long)loc[threadIdx.x]);
+  if (conf && threadIdx.x < M * M && loc[threadIdx.x]) atomicAdd(&conf[threadIdx.x], (unsigned long long)loc[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr,
@@ -290,15 +290,17 @@ int kd_kd_objective_final(const float* ce_kl, const float* slab_c, int64_t n_c, 
   return kd_check_launch("kd_kd_objective_final");
 }
 
-// conf[NC*NC] (uint64, ACCUMULATED into) and/or pred[B*HW] (int64 argmax over the class dim).
+// conf[M*M] (uint64, ACCUMULATED into) and/or pred[B*HW] (int64 argmax over all NC classes).  M is the width of the matrix
+// (SegmentationMetrics.num_classes), independent of NC: a pixel counts at [t, argmax] only when both are below M (trainer.py:18-26).
 int kd_argmax_confusion(const float* logits, const int64_t* target, int ignore_index, uint64_t* conf, int64_t* pred,
-                        int B, int NC, int HW, void* stream) {
-  KD_REQUIRE(logits && (conf || pred) && B > 0 && NC >= 1 && NC <= MAXC, KD_ERR_ARG, "kd_argmax_confusion: bad args");
+                        int B, int NC, int M, int HW, void* stream) {
+  KD_REQUIRE(logits && (conf || pred) && B > 0 && HW > 0 && NC >= 1 && NC <= MAXC, KD_ERR_ARG, "kd_argmax_confusion: bad args");
+  KD_REQUIRE(M >= 1 && M <= MAXC, KD_ERR_SHAPE, "kd_argmax_confusion: confusion matrix width %d unsupported (1..4)", M);
   const int64_t npix = (int64_t)B * HW;
   int64_t grid = (npix + 255) / 256;
   if (grid > 1024) grid = 1024;
   hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, logits, target,
-                     ignore_index, npix, HW, NC, (unsigned long long*)conf, pred);
+                     ignore_index, npix, HW, NC, M, (unsigned long long*)conf, pred);
   return kd_check_launch("kd_argmax_confusion");
 }
 

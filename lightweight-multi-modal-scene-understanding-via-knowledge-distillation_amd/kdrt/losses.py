@@ -31,6 +31,19 @@ def _check_target(logits, target):
                       f"[B, H, W] = {(B, H, W)} on {logits.device}")
 
 
+def _check_class_weights(logits, class_w):
+    """The loss kernels read class_w[y] for every label 0 <= y < NC without a bounds check of their own."""
+    if class_w is None:
+        return
+    NC = logits.shape[1]
+    if (not torch.is_tensor(class_w) or class_w.dtype != torch.float32 or class_w.device != logits.device
+            or class_w.dim() != 1 or class_w.numel() != NC or not class_w.is_contiguous()):
+        what = (f"{tuple(class_w.shape)} {class_w.dtype} on {class_w.device}" if torch.is_tensor(class_w)
+                else type(class_w).__name__)
+        raise KDError(f"class weights must be a contiguous float32 tensor of {NC} entries (the logits' class count) on "
+                      f"{logits.device}, got {what}")
+
+
 class _SegLossFn(torch.autograd.Function):
     """forward: loss values only; backward: one more fused call that writes dL/dlogits scaled by the
     upstream gradient read from device memory (no host sync, no extra elementwise pass)."""
@@ -52,6 +65,7 @@ class _SegLossFn(torch.autograd.Function):
         if target.dtype != torch.int64:
             raise KDError("segmentation target must be int64")
         _check_target(zs_c, target)
+        _check_class_weights(zs_c, class_w)
         losses = torch.empty(4, device=zs.device, dtype=torch.float32)
         _SegLossFn._call(zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, losses, None)
         ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha)
@@ -139,6 +153,7 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     if target.dtype != torch.int64:
         raise KDError("segmentation target must be int64")
     _check_target(zs_c, target)
+    _check_class_weights(zs_c, class_weights)
     B, NC, H, W = zs_c.shape
     vals = torch.empty(8, device=dev, dtype=torch.float32)        # [0:4] seg-loss values, [4] mse_cam, [5] mse_lidar, [6] total
     dzs = torch.empty_like(zs_c)
@@ -175,13 +190,21 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
 
 
 def confusion(logits, target, num_classes: int = 2, ignore_index: int = -1, out: Optional[torch.Tensor] = None):
-    """Accumulates into (or creates) an int64 [C, C] device confusion matrix; returns (conf, argmax)."""
+    """Accumulates into (or creates) an int64 [M, M] device confusion matrix, M = num_classes; returns (conf, argmax).
+    M need not be the logits' class count: a pixel counts at [t, argmax] when 0 <= t < M and argmax < M (trainer.py:18-26);
+    the returned argmax is over all classes."""
     ops.require_gpu_tensor(logits, "confusion")
     z = logits.detach().contiguous()
     B, NC, H, W = z.shape
+    M = int(num_classes)
     _check_target(z, target)
+    if target.dtype != torch.int64:
+        raise KDError("segmentation target must be int64")
     if out is None:
-        out = torch.zeros(num_classes, num_classes, device=z.device, dtype=torch.int64)
+        out = torch.zeros(M, M, device=z.device, dtype=torch.int64)
+    elif (out.dtype != torch.int64 or tuple(out.shape) != (M, M) or out.device != z.device or not out.is_contiguous()):
+        raise KDError(f"confusion: `out` must be a contiguous int64 [{M}, {M}] tensor on {z.device}, got "
+                      f"{tuple(out.shape)} {out.dtype} on {out.device}")
     pred = torch.empty(B, H, W, device=z.device, dtype=torch.int64)
-    lib.call("kd_argmax_confusion", P(z), P(target.contiguous()), int(ignore_index), P(out), P(pred), B, NC, H * W, stream())
+    lib.call("kd_argmax_confusion", P(z), P(target.contiguous()), int(ignore_index), P(out), P(pred), B, NC, M, H * W, stream())
     return out, pred
