@@ -236,6 +236,19 @@ int kd_lidar_seg_share_bwd(const float* y, const float* sc, const float* sh, int
                            const float* dout, const float* mean, const float* invstd, const int* seg_start,
                            const int* row_sorted, float* share, float* cnt_ws, float* partial, int64_t P,
                            int64_t ncells, int C, void* stream);
+/* The same pair without the second read of y: kd_lidar_seg_hold_fwd is kd_lidar_seg_max_fwd (row_sorted form, same grid bits)
+ * that also records, per (cell, channel), rawmax = the raw value of the maximum's first holder and holders = their number
+ * (one byte; 255 = "sweep the cell's rows": holders with different raw values, more than 254 of them, a row of more than
+ * 256 points).  kd_lidar_seg_hold_bwd derives share and partial from (dout, rawmax, holders) -- bit-identical to
+ * kd_lidar_seg_share_bwd for finite features -- and reads y and grid only for the cells marked 255.  rawmax [ncells, C]
+ * (rows of empty and >256-point cells are not written), holders [ncells, C] bytes, 4-byte aligned, every row written. */
+int kd_lidar_seg_hold_fwd(const float* y, const float* sc, const float* sh, int act, const int* seg_start,
+                          const int* row_sorted, float* grid, float* rawmax, uint8_t* holders, int64_t P, int64_t ncells,
+                          int C, void* stream);
+int kd_lidar_seg_hold_bwd(const float* y, const float* sc, const float* sh, int act, const float* grid,
+                          const float* rawmax, const uint8_t* holders, const float* dout, const float* mean,
+                          const float* invstd, const int* seg_start, const int* row_sorted, float* share, float* cnt_ws,
+                          float* partial, int64_t P, int64_t ncells, int C, void* stream);
 int kd_lidar_l2_dgrad(const float* Y2, int64_t ldy2, const int* rows, const float* grid, const float* share,
                       const float* al, const float* be, const float* ga, const float* sc2, const float* sh2, int act2,
                       const float* Wt, float* G1, int64_t ldg1, const float* Y1, int64_t ldy1, const float* sc1,

@@ -607,8 +607,13 @@ struct SegArgs {
   // sweep does, around the sensor) costs what a uniform one costs.  rowid [P]: grid row of each sorted point;
   // cnt [ncells, C]: holder counts of the long rows (float, exact); prow0: first slab row of the chunked kernel.
   int long_len; const int* rowid; float* cnt; int prow0;
+  // Holder tables (kd_lidar_seg_hold_fwd -> kd_lidar_seg_hold_bwd), per (cell, channel): rawmax = raw value of the first
+  // holder of the maximum in sorted point order; holders = how many rows hold it, one byte, SEG_HOLD_SWEEP = "not known
+  // here: sweep the cell's rows" (holders with different raw values, more than 254 holders, long row).
+  float* rawmax; uint8_t* holders;
 };
 constexpr int SEG_LONG = 256;
+constexpr int SEG_HOLD_SWEEP = 255;
 
 template <int VEC> struct SegVec;
 template <> struct SegVec<1> { typedef float type; };
@@ -671,8 +676,191 @@ __global__ __launch_bounds__(256) void seg_max_fwd_kernel(SegArgs a) {
   }
 }
 
-// TABLE: instead of G[P, C] the kernel leaves share[ncells, C] = dout / (number of holders) (0 where nobody holds) in
-// a.G; kd_lidar_l2_dgrad / _wgrad rebuild G on the fly from (y, grid, share), so the [P, C] gradient never exists.
+template <int VEC> __device__ __forceinline__ void seg_ld_bytes(int (&h)[VEC], const uint8_t* p) {
+  unsigned w;
+  if (VEC == 1) w = *p;
+  else if (VEC == 2) w = *reinterpret_cast<const uint16_t*>(p);
+  else w = *reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) h[j] = (int)((w >> (8 * j)) & 0xffu);
+}
+template <int VEC> __device__ __forceinline__ void seg_st_bytes(uint8_t* p, const int (&h)[VEC]) {
+  unsigned w = 0;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) w |= (unsigned)h[j] << (8 * j);
+  if (VEC == 1) *p = (uint8_t)w;
+  else if (VEC == 2) *reinterpret_cast<uint16_t*>(p) = (uint16_t)w;
+  else *reinterpret_cast<uint32_t*>(p) = w;
+}
+
+// seg_max_fwd_kernel for sorted rows that also records, next to each running maximum, what the backward needs to know
+// about its holders (rows with v > 0 && v == max): their number and the raw value of the first one.  All holders of a
+// (cell, channel) share the activated value; when they also share the raw value bit for bit (duplicated points -- or a
+// single holder, the usual case) the backward's sums follow from (rawmax, holders) alone.  Every row of `holders` is
+// written (0 for empty cells); rows of rawmax only for non-empty cells of at most long_len points.
+template <int VEC>
+__global__ __launch_bounds__(256) void seg_hold_fwd_kernel(SegArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int c0 = lane * VEC;
+  float sc[VEC], sh[VEC];
+  seg_ld<VEC>(sc, a.sc + c0);
+  seg_ld<VEC>(sh, a.sh + c0);
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < a.ncells; row += nw) {
+    const int s = __builtin_amdgcn_readfirstlane(a.start[row]);
+    const int e = __builtin_amdgcn_readfirstlane(a.start[row + 1]);
+    float m[VEC], raw[VEC];
+    int cnt[VEC], mixed[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) { m[j] = 0.f; raw[j] = 0.f; cnt[j] = 0; mixed[j] = 0; }
+    if (e - s > a.long_len) {                            // long row: zero here, maxima from seg_long_kernel's atomics
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) cnt[j] = SEG_HOLD_SWEEP;
+      seg_st<VEC>(a.grid + row * a.C + c0, m);
+      seg_st_bytes<VEC>(a.holders + row * a.C + c0, cnt);
+      continue;
+    }
+    // v > m: a new maximum with one holder (+0 start, NaN and -0 never win: same bits as seg_max_fwd_kernel);
+    // v == m > 0: one more holder of the current one
+#define KD_SEG_HOLD_STEP(rv, j)                                                              \
+    do {                                                                                     \
+      const float v = kd_act(kd_affine(rv, sc[j], sh[j]), a.act);                            \
+      const bool gt = v > m[j], eq = v == m[j] && v > 0.f;                                   \
+      const int differs = __float_as_uint(rv) != __float_as_uint(raw[j]) ? 1 : 0;            \
+      cnt[j] = gt ? 1 : cnt[j] + (eq ? 1 : 0);                                               \
+      mixed[j] = gt ? 0 : mixed[j] | (eq ? differs : 0);                                     \
+      raw[j] = gt ? rv : raw[j];                                                             \
+      m[j] = gt ? v : m[j];                                                                  \
+    } while (0)
+    int i = s;
+    for (; i + 4 <= e; i += 4) {
+      float r[4][VEC];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) seg_ld<VEC>(r[u], a.y + (int64_t)(i + u) * a.C + c0);
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) KD_SEG_HOLD_STEP(r[u][j], j);
+    }
+    for (; i < e; ++i) {
+      float r[VEC];
+      seg_ld<VEC>(r, a.y + (int64_t)i * a.C + c0);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) KD_SEG_HOLD_STEP(r[j], j);
+    }
+#undef KD_SEG_HOLD_STEP
+    seg_st<VEC>(a.grid + row * a.C + c0, m);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) cnt[j] = (mixed[j] || cnt[j] >= SEG_HOLD_SWEEP) ? SEG_HOLD_SWEEP : cnt[j];
+    seg_st_bytes<VEC>(a.holders + row * a.C + c0, cnt);
+    if (s != e) seg_st<VEC>(a.rawmax + row * a.C + c0, raw);
+  }
+}
+
+// One grid row [s, e) of the scatter-max backward: sweep 1 counts the holders of the row's maximum per channel, sweep 2
+// hands every holder share = dout / holders and adds its terms to the BatchNorm-backward sums s1 = sum G, s2 = sum G * xhat.
+// TABLE: instead of G[P, C] the row leaves share[C] (0 where nobody holds) in a.G; kd_lidar_l2_dgrad / _wgrad rebuild G on
+// the fly from (y, grid, share), so the [P, C] gradient never exists.
+template <int VEC, bool PERM, bool TABLE>
+__device__ __forceinline__ void seg_row_bwd(const SegArgs& a, int64_t row, int s, int e, int c0, const float (&sc)[VEC],
+                                            const float (&sh)[VEC], const float (&mu)[VEC], const float (&inv)[VEC],
+                                            float (&s1)[VEC], float (&s2)[VEC]) {
+  float mx[VEC], d[VEC];
+  seg_ld<VEC>(mx, a.grid + row * a.C + c0);
+  seg_ld<VEC>(d, a.dout + row * a.C + c0);
+  int cnt[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) cnt[j] = 0;
+  // (round 4: a single-load fast path for rows of at most 16 points -- all rows in registers, both passes from them -- measured
+  // 0.4 ms per step SLOWER than the two sweeps below (75.75 vs 75.3 ms, same box): 131 registers cut the occupancy from 8 to 3
+  // waves per SIMD, and the second sweep's L2 hits were never the cost.  Not kept.)
+  // sweep 1: holders per channel
+  int i = s;
+  for (; i + 4 <= e; i += 4) {
+    float r[4][VEC];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t p = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i + u]) : i + u);
+      seg_ld<VEC>(r[u], a.y + p * a.C + c0);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float v = kd_act(kd_affine(r[u][j], sc[j], sh[j]), a.act);
+        cnt[j] += (v > 0.f && v == mx[j]) ? 1 : 0;
+      }
+  }
+  for (; i < e; ++i) {
+    float r[VEC];
+    const int64_t p = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i]) : i);
+    seg_ld<VEC>(r, a.y + p * a.C + c0);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      const float v = kd_act(kd_affine(r[j], sc[j], sh[j]), a.act);
+      cnt[j] += (v > 0.f && v == mx[j]) ? 1 : 0;
+    }
+  }
+  float share[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) share[j] = d[j] / (float)cnt[j];   // only read where cnt >= 1
+  if (TABLE) {
+    float t[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) t[j] = cnt[j] > 0 ? share[j] : 0.f;
+    seg_st<VEC>(a.G + row * a.C + c0, t);
+  }
+  // sweep 2: the rows come back from L2 (a cell's points were read a few hundred cycles ago)
+  i = s;
+  for (; i + 4 <= e; i += 4) {
+    float r[4][VEC];
+    int64_t p[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      p[u] = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i + u]) : i + u);
+      seg_ld<VEC>(r[u], a.y + p[u] * a.C + c0);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float g[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        const float v = kd_act(kd_affine(r[u][j], sc[j], sh[j]), a.act);
+        g[j] = (v > 0.f && v == mx[j]) ? share[j] : 0.f;
+        s1[j] += g[j];
+        s2[j] = fmaf(g[j], (r[u][j] - mu[j]) * inv[j], s2[j]);
+      }
+      if (!TABLE) seg_st<VEC>(a.G + p[u] * a.C + c0, g);
+    }
+  }
+  for (; i < e; ++i) {
+    float r[VEC], g[VEC];
+    const int64_t p = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i]) : i);
+    seg_ld<VEC>(r, a.y + p * a.C + c0);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      const float v = kd_act(kd_affine(r[j], sc[j], sh[j]), a.act);
+      g[j] = (v > 0.f && v == mx[j]) ? share[j] : 0.f;
+      s1[j] += g[j];
+      s2[j] = fmaf(g[j], (r[j] - mu[j]) * inv[j], s2[j]);
+    }
+    if (!TABLE) seg_st<VEC>(a.G + p * a.C + c0, g);
+  }
+}
+
+// partial[prow][2][C] <- the four waves' (s1, s2), summed in wave order
+template <int VEC>
+__device__ __forceinline__ void seg_stat_rows_out(const SegArgs& a, float (&red)[4][2][64 * VEC], int64_t prow, int wave, int c0,
+                                                  const float (&s1)[VEC], const float (&s2)[VEC]) {
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { red[wave][0][c0 + j] = s1[j]; red[wave][1][c0 + j] = s2[j]; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * a.C; i += 256) {
+    const int st = i / a.C, c = i % a.C;
+    a.partial[(prow * 2 + st) * a.C + c] = red[0][st][c] + red[1][st][c] + red[2][st][c] + red[3][st][c];
+  }
+}
+
 template <int VEC, bool PERM, bool TABLE = false>
 __global__ __launch_bounds__(256) void seg_max_bwd_kernel(SegArgs a) {
   __shared__ float red[4][2][64 * VEC];
@@ -697,95 +885,68 @@ __global__ __launch_bounds__(256) void seg_max_bwd_kernel(SegArgs a) {
       seg_st<VEC>(a.cnt + row * a.C + c0, z);
       continue;
     }
-    float mx[VEC], d[VEC];
-    seg_ld<VEC>(mx, a.grid + row * a.C + c0);
+    seg_row_bwd<VEC, PERM, TABLE>(a, row, s, e, c0, sc, sh, mu, inv, s1, s2);
+  }
+  seg_stat_rows_out<VEC>(a, red, blockIdx.x, wave, c0, s1, s2);
+}
+
+// seg_max_bwd_kernel<VEC, false, true> from the holder tables of seg_hold_fwd_kernel: same grid, same wave -> cell
+// assignment and cell order, and per (cell, channel) the very additions that sweep 2 performs at the holders, in the same
+// order (a non-holder adds g = +0 there, which changes neither sum) -- so share and partial keep their bits while the
+// rows of y are not read at all.  A cell with a SEG_HOLD_SWEEP entry on any channel takes the two sweeps, in place.
+template <int VEC>
+__global__ __launch_bounds__(256) void seg_hold_bwd_kernel(SegArgs a) {
+  __shared__ float red[4][2][64 * VEC];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c0 = lane * VEC;
+  float sc[VEC], sh[VEC], mu[VEC], inv[VEC], s1[VEC], s2[VEC];
+  seg_ld<VEC>(sc, a.sc + c0);
+  seg_ld<VEC>(sh, a.sh + c0);
+  seg_ld<VEC>(mu, a.mean + c0);
+  seg_ld<VEC>(inv, a.invstd + c0);
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < a.ncells; row += nw) {
+    const int s = __builtin_amdgcn_readfirstlane(a.start[row]);
+    const int e = __builtin_amdgcn_readfirstlane(a.start[row + 1]);
+    if (s == e) continue;
+    if (e - s > a.long_len) {                            // long row: counted and shared out by the chunked kernels
+      float z[VEC];
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) z[j] = 0.f;
+      seg_st<VEC>(a.cnt + row * a.C + c0, z);
+      continue;
+    }
+    int h[VEC];
+    float d[VEC], raw[VEC];
+    seg_ld_bytes<VEC>(h, a.holders + row * a.C + c0);
     seg_ld<VEC>(d, a.dout + row * a.C + c0);
-    int cnt[VEC];
+    seg_ld<VEC>(raw, a.rawmax + row * a.C + c0);
+    bool sweep = false;
+    int hmax = 0;
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) cnt[j] = 0;
-    // (round 4: a single-load fast path for rows of at most 16 points -- all rows in registers, both passes from them -- measured
-    // 0.4 ms per step SLOWER than the two sweeps below (75.75 vs 75.3 ms, same box): 131 registers cut the occupancy from 8 to 3
-    // waves per SIMD, and the second sweep's L2 hits were never the cost.  Not kept.)
-    // sweep 1: holders per channel
-    int i = s;
-    for (; i + 4 <= e; i += 4) {
-      float r[4][VEC];
+    for (int j = 0; j < VEC; ++j) { sweep |= h[j] == SEG_HOLD_SWEEP; hmax = h[j] > hmax ? h[j] : hmax; }
+    if (__any(sweep)) {
+      seg_row_bwd<VEC, false, true>(a, row, s, e, c0, sc, sh, mu, inv, s1, s2);
+      continue;
+    }
+    float share[VEC], xhat[VEC];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int64_t p = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i + u]) : i + u);
-        seg_ld<VEC>(r[u], a.y + p * a.C + c0);
-      }
+    for (int j = 0; j < VEC; ++j) {
+      share[j] = h[j] > 0 ? d[j] / (float)h[j] : 0.f;
+      xhat[j] = (raw[j] - mu[j]) * inv[j];
+    }
+    seg_st<VEC>(a.G + row * a.C + c0, share);
+    for (int k = 0; k < hmax; ++k)
 #pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          const float v = kd_act(kd_affine(r[u][j], sc[j], sh[j]), a.act);
-          cnt[j] += (v > 0.f && v == mx[j]) ? 1 : 0;
+      for (int j = 0; j < VEC; ++j)
+        if (k < h[j]) {
+          s1[j] += share[j];
+          s2[j] = fmaf(share[j], xhat[j], s2[j]);
         }
-    }
-    for (; i < e; ++i) {
-      float r[VEC];
-      const int64_t p = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i]) : i);
-      seg_ld<VEC>(r, a.y + p * a.C + c0);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float v = kd_act(kd_affine(r[j], sc[j], sh[j]), a.act);
-        cnt[j] += (v > 0.f && v == mx[j]) ? 1 : 0;
-      }
-    }
-    float share[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) share[j] = d[j] / (float)cnt[j];   // only read where cnt >= 1
-    if (TABLE) {
-      float t[VEC];
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) t[j] = cnt[j] > 0 ? share[j] : 0.f;
-      seg_st<VEC>(a.G + row * a.C + c0, t);
-    }
-    // sweep 2: the rows come back from L2 (a cell's points were read a few hundred cycles ago)
-    i = s;
-    for (; i + 4 <= e; i += 4) {
-      float r[4][VEC];
-      int64_t p[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        p[u] = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i + u]) : i + u);
-        seg_ld<VEC>(r[u], a.y + p[u] * a.C + c0);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float g[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          const float v = kd_act(kd_affine(r[u][j], sc[j], sh[j]), a.act);
-          g[j] = (v > 0.f && v == mx[j]) ? share[j] : 0.f;
-          s1[j] += g[j];
-          s2[j] = fmaf(g[j], (r[u][j] - mu[j]) * inv[j], s2[j]);
-        }
-        if (!TABLE) seg_st<VEC>(a.G + p[u] * a.C + c0, g);
-      }
-    }
-    for (; i < e; ++i) {
-      float r[VEC], g[VEC];
-      const int64_t p = (PERM ? __builtin_amdgcn_readfirstlane(a.perm[i]) : i);
-      seg_ld<VEC>(r, a.y + p * a.C + c0);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float v = kd_act(kd_affine(r[j], sc[j], sh[j]), a.act);
-        g[j] = (v > 0.f && v == mx[j]) ? share[j] : 0.f;
-        s1[j] += g[j];
-        s2[j] = fmaf(g[j], (r[j] - mu[j]) * inv[j], s2[j]);
-      }
-      if (!TABLE) seg_st<VEC>(a.G + p * a.C + c0, g);
-    }
   }
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) { red[wave][0][c0 + j] = s1[j]; red[wave][1][c0 + j] = s2[j]; }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * a.C; i += 256) {
-    const int st = i / a.C, c = i % a.C;
-    a.partial[((int64_t)blockIdx.x * 2 + st) * a.C + c] = red[0][st][c] + red[1][st][c] + red[2][st][c] + red[3][st][c];
-  }
+  seg_stat_rows_out<VEC>(a, red, blockIdx.x, wave, c0, s1, s2);
 }
 
 // ---- chunked kernels for the long rows: wave w owns sorted rows [64w, 64w + 64) -----------------------------------
@@ -1085,6 +1246,63 @@ int kd_lidar_seg_share_bwd(const float* y, const float* sc, const float* sh, int
     hipLaunchKernelGGL((seg_long_kernel<4, 2>), gl, bl, 0, st, a);
   }
   return kd_check_launch("kd_lidar_seg_share_bwd");
+}
+
+// kd_lidar_seg_max_fwd (sorted rows, row_sorted given) that also leaves the holder tables for kd_lidar_seg_hold_bwd:
+// rawmax [ncells, C] floats and holders [ncells, C] bytes (4-byte aligned); see SegArgs.  Same grid, bit for bit.
+int kd_lidar_seg_hold_fwd(const float* y, const float* sc, const float* sh, int act, const int* seg_start, const int* row_sorted,
+                          float* grid, float* rawmax, uint8_t* holders, int64_t P, int64_t ncells, int C, void* stream) {
+  KD_REQUIRE(y && sc && sh && seg_start && row_sorted && grid && rawmax && holders && ncells > 0 && P > 0, KD_ERR_ARG,
+             "kd_lidar_seg_hold_fwd: bad args");
+  KD_REQUIRE(C == 64 || C == 128 || C == 256, KD_ERR_SHAPE, "kd_lidar_seg_hold_fwd: C must be 64, 128 or 256 (got %d)", C);
+  KD_REQUIRE(act == KD_ACT_RELU || act == KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_seg_hold_fwd: needs a non-negative activation");
+  KD_REQUIRE((uintptr_t)holders % 4 == 0, KD_ERR_ARG, "kd_lidar_seg_hold_fwd: holders must be 4-byte aligned");
+  SegArgs a{y, sc, sh, act, seg_start, nullptr, grid, nullptr, nullptr, nullptr, nullptr, nullptr, ncells, C,
+            SEG_LONG, row_sorted, nullptr, 0, rawmax, holders};
+  const dim3 gr(seg_grid(ncells)), gl(seg_long_grid(P)), bl(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (C == 64) {
+    hipLaunchKernelGGL((seg_hold_fwd_kernel<1>), gr, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<1, 0>), gl, bl, 0, st, a);
+  } else if (C == 128) {
+    hipLaunchKernelGGL((seg_hold_fwd_kernel<2>), gr, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<2, 0>), gl, bl, 0, st, a);
+  } else {
+    hipLaunchKernelGGL((seg_hold_fwd_kernel<4>), gr, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<4, 0>), gl, bl, 0, st, a);
+  }
+  return kd_check_launch("kd_lidar_seg_hold_fwd");
+}
+
+// kd_lidar_seg_share_bwd from the tables of kd_lidar_seg_hold_fwd (same y, sc, sh, act, seg_start): the same share and the
+// same partial [kd_lidar_seg_share_stat_rows][2][C], bit for bit, for finite features.  y and grid are read only for the
+// cells marked for the sweep and for the rows with more than 256 points.
+int kd_lidar_seg_hold_bwd(const float* y, const float* sc, const float* sh, int act, const float* grid, const float* rawmax,
+                          const uint8_t* holders, const float* dout, const float* mean, const float* invstd, const int* seg_start,
+                          const int* row_sorted, float* share, float* cnt_ws, float* partial, int64_t P, int64_t ncells, int C,
+                          void* stream) {
+  KD_REQUIRE(y && sc && sh && grid && rawmax && holders && dout && mean && invstd && seg_start && row_sorted && share && cnt_ws &&
+             partial && ncells > 0 && P > 0, KD_ERR_ARG, "kd_lidar_seg_hold_bwd: bad args");
+  KD_REQUIRE(C == 64 || C == 128 || C == 256, KD_ERR_SHAPE, "kd_lidar_seg_hold_bwd: C must be 64, 128 or 256 (got %d)", C);
+  KD_REQUIRE((uintptr_t)holders % 4 == 0, KD_ERR_ARG, "kd_lidar_seg_hold_bwd: holders must be 4-byte aligned");
+  SegArgs a{y, sc, sh, act, seg_start, nullptr, const_cast<float*>(grid), dout, mean, invstd, share, partial, ncells, C,
+            SEG_LONG, row_sorted, cnt_ws, seg_grid(ncells), const_cast<float*>(rawmax), const_cast<uint8_t*>(holders)};
+  const dim3 gr(seg_grid(ncells)), gl(seg_long_grid(P)), bl(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (C == 64) {
+    hipLaunchKernelGGL((seg_hold_bwd_kernel<1>), gr, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<1, 1>), gl, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<1, 2>), gl, bl, 0, st, a);
+  } else if (C == 128) {
+    hipLaunchKernelGGL((seg_hold_bwd_kernel<2>), gr, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<2, 1>), gl, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<2, 2>), gl, bl, 0, st, a);
+  } else {
+    hipLaunchKernelGGL((seg_hold_bwd_kernel<4>), gr, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<4, 1>), gl, bl, 0, st, a);
+    hipLaunchKernelGGL((seg_long_kernel<4, 2>), gl, bl, 0, st, a);
+  }
+  return kd_check_launch("kd_lidar_seg_hold_bwd");
 }
 
 }  // extern "C"

@@ -1022,6 +1022,9 @@ _SCATTER_MODE = "sorted"
 # with sorted points: hand the scatter-max gradient to the last layer's backward GEMMs as per-cell tables (default) or
 # as the materialised [points, C] tensor (False: tests)
 _SCATTER_TABLES = True
+# with the tables: the forward also records each maximum's holders (first raw value, count), and the backward derives the
+# tables from those instead of reading the last layer's output twice more (default); False: kd_lidar_seg_share_bwd (A/B)
+_SCATTER_HOLDERS = True
 # the whole eval-mode encoder (point MLP + scatter-max) in one kernel (csrc/kd_lidar_infer.hip); False: layer by layer
 _LIDAR_FUSED_INFER = True
 
@@ -1169,7 +1172,15 @@ class LidarFn(torch.autograd.Function):
         C = cur.C
         grid = torch.empty(B * H * W, C, device=pts.device, dtype=torch.float32)
         ctx.seg = seg
-        if seg is not None:
+        ctx.hold = None
+        if (mode == "points" and training and _SCATTER_TABLES and _SCATTER_HOLDERS and recs[-1].spec.kind == "pw"
+                and recs[-1].inp.virt is None and recs[-1].inp.bnc is not None):      # the backward's table-path condition
+            rawmax = torch.empty(B * H * W, C, device=pts.device, dtype=torch.float32)
+            holders = torch.empty(B * H * W, C, device=pts.device, dtype=torch.uint8)
+            lib.call("kd_lidar_seg_hold_fwd", P(cur.raw), P(cur.sc), P(cur.sh), cur.act, P(seg[1]), P(seg[0]), P(grid),
+                     P(rawmax), P(holders), B * N, B * H * W, C, stream())
+            ctx.hold = (rawmax, holders)
+        elif seg is not None:
             # forward max and backward tie split over the segments: atomic-free
             lib.call("kd_lidar_seg_max_fwd", P(cur.raw), P(cur.sc), P(cur.sh), cur.act, P(seg[1]), P(seg[2]),
                      P(seg[0]) if seg[2] is None else None, P(grid), B * N, B * H * W, C, stream())
@@ -1195,8 +1206,13 @@ class LidarFn(torch.autograd.Function):
             partial = torch.empty(rows * 2 * C, device=dev, dtype=torch.float32)
             share = torch.empty(B * H * W, C, device=dev, dtype=torch.float32)
             cnt_ws = torch.empty(B * H * W, C, device=dev, dtype=torch.float32)
-            lib.call("kd_lidar_seg_share_bwd", P(cur.raw), P(cur.sc), P(cur.sh), cur.act, P(ctx.grid), P(dm), P(cur.bnc.mean),
-                     P(cur.bnc.invstd), P(seg_start), P(row_sorted), P(share), P(cnt_ws), P(partial), Pn, B * H * W, C, stream())
+            if ctx.hold is not None:
+                lib.call("kd_lidar_seg_hold_bwd", P(cur.raw), P(cur.sc), P(cur.sh), cur.act, P(ctx.grid), P(ctx.hold[0]),
+                         P(ctx.hold[1]), P(dm), P(cur.bnc.mean), P(cur.bnc.invstd), P(seg_start), P(row_sorted), P(share),
+                         P(cnt_ws), P(partial), Pn, B * H * W, C, stream())
+            else:
+                lib.call("kd_lidar_seg_share_bwd", P(cur.raw), P(cur.sc), P(cur.sh), cur.act, P(ctx.grid), P(dm), P(cur.bnc.mean),
+                         P(cur.bnc.invstd), P(seg_start), P(row_sorted), P(share), P(cnt_ws), P(partial), Pn, B * H * W, C, stream())
             grads, _ = chain_backward(ctx.recs, ("GS", (row_sorted, ctx.grid, share), partial, rows), need_input_grad=False)
             return (None, None, None, None, None, *grads)
         G = torch.empty(Pn, C, device=dev, dtype=torch.float32)
