@@ -358,6 +358,20 @@ int kd_semantic_remap(const int64_t* raw, int64_t n, uint64_t remap_bits, int64_
 int kd_points_prepare(const float* x, const float* y, const float* z, const float* intensity, const int64_t* choice,
                       int64_t n, int64_t max_points, float* out, void* stream);
 int kd_image_u8hwc_to_f32chw(const uint8_t* in, float* out, int H, int W, void* stream);
+/* Whole-batch forms, one launch each.  in[B,H,W,3] -> out[B,3,H,W], every frame with the bits of the per-frame call. */
+int kd_image_u8hwc_to_f32chw_batch(const uint8_t* in, float* out, int B, int H, int W, void* stream);
+/* out[B,max_points,4] from B ragged frames (offsets as in kd_bev_rasterize; x, y, z, intensity concatenated).  A frame
+ * of n <= max_points points is stacked and zero-padded (the bits of kd_points_prepare with choice = NULL).  A longer
+ * frame is cut to a uniform subset of exactly max_points rows without replacement, chosen on the device: point index
+ * j gets the 32-bit key  Philox-4x32-10(counter = (j, 0, frame_keys[b] low word, high word), key = (seed low word,
+ * high word))[word 0]  (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85); the kept rows are
+ * the max_points smallest (key, j) pairs in lexicographic order and are written in ascending j.  A frame's rows so
+ * depend on (seed, frame_keys[b], n, max_points) and its own points only -- not on the batch around it, the launch
+ * shape or any atomics order.  frame_keys: device uint64 [B].  One workgroup per frame; no workspace.
+ * tests/_input_batch_ref.py is the numpy mirror of the rule. */
+int kd_points_prepare_batch(const float* x, const float* y, const float* z, const float* intensity, const int64_t* offsets,
+                            const uint64_t* frame_keys, int B, int64_t n_total, int64_t max_points, uint64_t seed, float* out,
+                            void* stream);
 
 /* ---- losses, metric, optimiser (trainer.py:18-37,55-56,86-90; KD terms are build-defined) ------ */
 size_t kd_seg_loss_ws_bytes(int64_t npix);

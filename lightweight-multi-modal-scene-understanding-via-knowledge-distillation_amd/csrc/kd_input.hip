@@ -5,7 +5,11 @@
 //     cell and a second kernel reads the winner's label: order-independent, bit-exact, one pass over the points.
 //   * point stacking + zero padding / subsample gather (:113-127)
 //   * uint8 HWC image -> float32 CHW / 255 (:108-111)
-// All HBM-bound byte/integer work: coalesced streams, no LDS needed.
+//   * the same two for a whole ragged batch in one launch each; a frame longer than max_points is cut to a uniform
+//     subset ON THE DEVICE: a counter-based key per point index (Philox-4x32-10), radix-select of the max_points-th
+//     smallest (key, index) pair over an LDS histogram, ordered compaction of the kept rows -- no permutation of the
+//     sweep, no sort, nothing stored per point.
+// All HBM-bound byte/integer work: coalesced streams; LDS only for the select's histogram and block scans.
 #include "kd_common.h"
 
 namespace {
@@ -87,6 +91,138 @@ __global__ __launch_bounds__(256) void image_chw_kernel(const uint8_t* __restric
   }
 }
 
+// ---- batched forms ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void image_chw_batch_kernel(const uint8_t* __restrict__ in, float* __restrict__ out,
+                                                              int64_t HW, int64_t total) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < total; p += (int64_t)gridDim.x * 256) {
+    const int64_t b = p / HW, q = p - b * HW;
+    const uint8_t* s = in + p * 3;
+    float* d = out + b * 3 * HW + q;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[(int64_t)c * HW] = __fdiv_rn((float)s[c], 255.f);
+  }
+}
+
+// Philox-4x32-10 (Salmon et al., SC'11), word 0 of the output block
+__device__ __forceinline__ uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+
+constexpr int kSelThreads = 1024;                // one workgroup per frame
+constexpr int kSelWaves = kSelThreads / 64;
+constexpr int kSelItems = 4;                     // consecutive point indices per thread and compaction chunk
+
+struct SelShared {
+  uint32_t hist[256];
+  uint32_t wave_tot[kSelWaves];
+  uint32_t prefix, remaining;
+};
+
+// exclusive prefix sum of `v` over the workgroup in thread order (+ the workgroup total); all threads must call it
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wave_tot, uint32_t& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  __syncthreads();                               // the previous call's readers are done with wave_tot
+  if (lane == 63) wave_tot[wave] = inc;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < kSelWaves; ++w) {
+    const uint32_t t = wave_tot[w];
+    before += w < wave ? t : 0u;
+    all += t;
+  }
+  total = all;
+  return before + inc - v;
+}
+
+__global__ __launch_bounds__(kSelThreads) void points_prepare_batch_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const float* __restrict__ w,
+    const int64_t* __restrict__ off, const uint64_t* __restrict__ frame_key, uint64_t seed, int64_t max_points,
+    float* __restrict__ out) {
+  __shared__ SelShared sh;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int64_t base = off[b];
+  const int64_t n = off[b + 1] - base;
+  x += base; y += base; z += base; w += base;
+  out += (int64_t)b * max_points * 4;
+  if (n <= max_points) {                         // stack + zero padding: the bits of kd_points_prepare(choice = NULL)
+    for (int64_t j = tid; j < max_points; j += kSelThreads)
+      kd_st4(out + j * 4, j < n ? make_float4(x[j], y[j], z[j], w[j]) : kd_zero4());
+    return;
+  }
+  const uint64_t fk = frame_key[b];
+  const uint32_t c2 = (uint32_t)fk, c3 = (uint32_t)(fk >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const uint32_t nn = (uint32_t)n;               // the host checked n_total < 2^31
+
+  // radix select, most significant byte first: after the four passes `prefix` is the key T of the max_points-th
+  // smallest (key, index) pair and `remaining` how many points with key == T are kept (those of lowest index)
+  uint32_t prefix = 0, remaining = (uint32_t)max_points;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) sh.hist[tid] = 0;
+    __syncthreads();
+    const uint32_t hi_mask = shift == 24 ? 0u : ~0u << (shift + 8);
+    for (uint32_t j = tid; j < nn; j += kSelThreads) {
+      const uint32_t k = philox_word0(j, 0u, c2, c3, k0, k1);
+      if ((k & hi_mask) == prefix) atomicAdd(&sh.hist[(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const uint32_t h = tid < 256 ? sh.hist[tid] : 0u;
+    uint32_t total;
+    const uint32_t below = block_excl_scan(h, sh.wave_tot, total);
+    if (tid < 256 && below < remaining && remaining <= below + h) {          // exactly one bin
+      sh.prefix = prefix | ((uint32_t)tid << shift);
+      sh.remaining = remaining - below;
+    }
+    __syncthreads();
+    prefix = sh.prefix;
+    remaining = sh.remaining;
+  }
+
+  // ordered compaction over index chunks: a kept row's slot = (# keys < T before it) + min(# keys == T before it, remaining)
+  uint32_t less_before = 0, tie_before = 0;
+  constexpr uint32_t kChunk = kSelThreads * kSelItems;
+  for (uint32_t c0 = 0; c0 < nn; c0 += kChunk) {
+    const uint32_t j0 = c0 + (uint32_t)tid * kSelItems;
+    uint32_t less[kSelItems], tie[kSelItems], packed = 0;                    // chunk counts <= 4096: 16 bits each
+#pragma unroll
+    for (int i = 0; i < kSelItems; ++i) {
+      const uint32_t j = j0 + i;
+      const uint32_t k = philox_word0(j, 0u, c2, c3, k0, k1);
+      less[i] = (j < nn && k < prefix) ? 1u : 0u;
+      tie[i] = (j < nn && k == prefix) ? 1u : 0u;
+      packed += less[i] | (tie[i] << 16);
+    }
+    uint32_t total;
+    const uint32_t ex = block_excl_scan(packed, sh.wave_tot, total);
+    uint32_t nl = less_before + (ex & 0xffffu), nt = tie_before + (ex >> 16);
+#pragma unroll
+    for (int i = 0; i < kSelItems; ++i) {
+      const uint32_t j = j0 + i;
+      if (less[i] || (tie[i] && nt < remaining)) {
+        const uint32_t slot = nl + (nt < remaining ? nt : remaining);
+        kd_st4(out + (int64_t)slot * 4, make_float4(x[j], y[j], z[j], w[j]));
+      }
+      nl += less[i];
+      nt += tie[i];
+    }
+    less_before += total & 0xffffu;
+    tie_before += total >> 16;
+  }
+}
+
 int grid_for(int64_t n) {
   int64_t g = (n + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
@@ -139,6 +275,25 @@ int kd_image_u8hwc_to_f32chw(const uint8_t* in, float* out, int H, int W, void* 
   KD_REQUIRE(in && out && H > 0 && W > 0, KD_ERR_ARG, "kd_image_u8hwc_to_f32chw: bad args");
   hipLaunchKernelGGL(image_chw_kernel, dim3(grid_for((int64_t)H * W)), dim3(256), 0, (hipStream_t)stream, in, out, H * W);
   return kd_check_launch("kd_image_u8hwc_to_f32chw");
+}
+
+int kd_image_u8hwc_to_f32chw_batch(const uint8_t* in, float* out, int B, int H, int W, void* stream) {
+  KD_REQUIRE(in && out && B > 0 && H > 0 && W > 0, KD_ERR_ARG, "kd_image_u8hwc_to_f32chw_batch: bad args");
+  const int64_t HW = (int64_t)H * W;
+  hipLaunchKernelGGL(image_chw_batch_kernel, dim3(grid_for(B * HW)), dim3(256), 0, (hipStream_t)stream, in, out, HW, B * HW);
+  return kd_check_launch("kd_image_u8hwc_to_f32chw_batch");
+}
+
+int kd_points_prepare_batch(const float* x, const float* y, const float* z, const float* intensity, const int64_t* offsets,
+                            const uint64_t* frame_keys, int B, int64_t n_total, int64_t max_points, uint64_t seed, float* out,
+                            void* stream) {
+  KD_REQUIRE(offsets && frame_keys && out && B > 0 && max_points > 0 && n_total >= 0, KD_ERR_ARG, "kd_points_prepare_batch: bad args");
+  KD_REQUIRE(n_total == 0 || (x && y && z && intensity), KD_ERR_ARG, "kd_points_prepare_batch: null coordinate arrays");
+  KD_REQUIRE(n_total < (int64_t)1 << 31 && max_points < (int64_t)1 << 31, KD_ERR_SHAPE, "kd_points_prepare_batch: too many points");
+  KD_REQUIRE(kd_aligned16(out), KD_ERR_ALIGN, "kd_points_prepare_batch: out must be 16-byte aligned");
+  hipLaunchKernelGGL(points_prepare_batch_kernel, dim3(B), dim3(kSelThreads), 0, (hipStream_t)stream, x, y, z, intensity,
+                     offsets, frame_keys, seed, max_points, out);
+  return kd_check_launch("kd_points_prepare_batch");
 }
 
 }  // extern "C"

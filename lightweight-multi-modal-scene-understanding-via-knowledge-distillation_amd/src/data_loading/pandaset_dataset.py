@@ -8,7 +8,10 @@ rasterize_bev (:23-45, the reference's 44 ms/frame Python loop).  `dataset[i]` r
 dictionary with CUDA tensors.  The loaders from `create_pandaset_dataloaders` keep DataLoader worker processes for
 the host I/O only (`load_raw`: decode + unpickle, nothing touches the GPU there) and prepare each whole batch on
 the device in the consuming process (`DeviceBatchLoader`: one rasteriser launch per batch over ragged frames);
-`.to(device)` in the trainer is then a no-op.
+`.to(device)` in the trainer is then a no-op.  `DeviceBatchLoader(prefetch >= 1)` prepares batch k+1 while the step
+consumes batch k: one host-to-device copy per tensor from pinned staging buffers and three launches per batch
+(`prepare_batch_staged`) on a side stream; long sweeps are then cut by the device sampler of kd_points_prepare_batch,
+keyed on (`sample_seed`, epoch, dataset index).
 
 `SyntheticPandaSet` serves frames of the same contract when there is no dataset on disk:
     image        float32 [3, 256, 256] in [0, 1]
@@ -17,6 +20,7 @@ the device in the consuming process (`DeviceBatchLoader`: one rasteriser launch 
 """
 import gc
 import os
+from collections import deque
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -109,6 +113,48 @@ def image_to_chw(img_u8_hwc) -> torch.Tensor:
     return out
 
 
+class StagingSet:
+    """Pinned host buffers of ONE batch in flight (grow-only) + the event after its host-to-device copies: the buffers
+    are not refilled before that event has completed."""
+
+    def __init__(self):
+        self.cols = self.cls = self.img = self.meta = None
+        self.copied = None
+
+    def _fit(self, name: str, numel: int, dtype) -> np.ndarray:
+        buf = getattr(self, name)
+        if buf is None or buf.numel() < numel:
+            buf = torch.empty(max(numel, 1), dtype=dtype).pin_memory()
+            setattr(self, name, buf)
+        return buf.numpy()
+
+    def fill(self, raws: Sequence[Dict[str, object]], frame_keys: Sequence[int]):
+        """-> (lens, image shape) after packing the batch: cols = x | y | z | i (each n_total float32), cls (n_total
+        int64), img [B,H,W,3] uint8, meta = offsets [B+1] | frame keys [B] (int64)."""
+        if self.copied is not None:
+            self.copied.synchronize()
+        B = len(raws)
+        lens = [int(np.shape(r["x"])[0]) for r in raws]
+        n = sum(lens)
+        if any(int(np.shape(r[k])[0]) != m for r, m in zip(raws, lens) for k in ("y", "z", "i", "class")):
+            raise KDError("x, y, z, i and class must have the same length per frame")
+        cols = self._fit("cols", 4 * n, torch.float32)
+        for c, k in enumerate("xyzi"):
+            np.concatenate([np.asarray(r[k], np.float32).reshape(-1) for r in raws], out=cols[c * n:(c + 1) * n])
+        np.concatenate([np.asarray(r["class"], np.int64).reshape(-1) for r in raws], out=self._fit("cls", n, torch.int64)[:n])
+        shape = tuple(np.shape(raws[0]["image_u8"]))
+        if len(shape) != 3 or shape[2] != 3 or any(tuple(np.shape(r["image_u8"])) != shape for r in raws):
+            raise KDError(f"expected HxWx3 uint8 images of one size per batch, got {[np.shape(r['image_u8']) for r in raws]}")
+        img = self._fit("img", B * shape[0] * shape[1] * 3, torch.uint8)[: B * shape[0] * shape[1] * 3].reshape(B, *shape)
+        for b, r in enumerate(raws):
+            img[b] = r["image_u8"]
+        meta = self._fit("meta", 2 * B + 1, torch.int64)
+        meta[0] = 0
+        np.cumsum(lens, out=meta[1:B + 1])
+        meta[B + 1:2 * B + 1] = np.asarray([k & 0xFFFFFFFFFFFFFFFF for k in frame_keys], np.uint64).view(np.int64)
+        return lens, shape
+
+
 class PandaSetDataset(Dataset):
     """2-class version: background (0) and drivable (1, includes lanes)."""
 
@@ -165,6 +211,51 @@ class PandaSetDataset(Dataset):
         img = torch.stack([image_to_chw(r["image_u8"]) for r in raws])
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
 
+    def prepare_batch_staged(self, raws: Sequence[Dict[str, object]], staging: StagingSet, side: "torch.cuda.Stream",
+                             frame_keys: Sequence[int], sample_seed: int = 0, ws_holder: list = None) -> Dict[str, object]:
+        """`prepare_batch` for a whole batch at once, enqueued on the stream `side`: one host-to-device copy per tensor
+        from the pinned `staging` set (packed point columns, class ids, uint8 images, offsets + frame keys), then three
+        launches (rasteriser, batched points, batched images).  Sweeps longer than max_points are cut by the device
+        sampler of kd_points_prepare_batch under (`sample_seed`, frame key).  The tensors returned belong to `side`:
+        a consumer on another stream waits for an event recorded after this call and tells the allocator
+        (`record_stream`).  `ws_holder`: a one-element list that keeps the rasteriser's workspace of this stream."""
+        if not torch.cuda.is_available():
+            raise KDError("input preparation runs on the MI355X; there is no CPU fallback")
+        B = len(raws)
+        if B == 0:
+            raise KDError("prepare_batch_staged needs at least one frame")
+        lens, (H, W, _) = staging.fill(raws, frame_keys)
+        n = sum(lens)
+        GH, GW = int(self.grid_size[0]), int(self.grid_size[1])
+        x0, x1, y0, y1 = self.pc_range
+        ws_holder = [None] if ws_holder is None else ws_holder
+        with torch.cuda.stream(side):
+            cols = torch.empty(max(4 * n, 1), dtype=torch.float32, device="cuda")
+            cls = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
+            img8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device="cuda")
+            meta = torch.empty(2 * B + 1, dtype=torch.int64, device="cuda")
+            cols[:4 * n].copy_(staging.cols[:4 * n], non_blocking=True)
+            cls[:n].copy_(staging.cls[:n], non_blocking=True)
+            img8.view(-1).copy_(staging.img[:img8.numel()], non_blocking=True)
+            meta.copy_(staging.meta[:2 * B + 1], non_blocking=True)
+            staging.copied = torch.cuda.Event()
+            staging.copied.record(side)
+            x, y, z, w = (cols[c * n:(c + 1) * n] for c in range(4))
+            off, keys = meta[:B + 1], meta[B + 1:]
+            seg = torch.empty(B, GH, GW, dtype=torch.int64, device="cuda")
+            pts = torch.empty(B, self.max_points, 4, dtype=torch.float32, device="cuda")
+            img = torch.empty(B, 3, H, W, dtype=torch.float32, device="cuda")
+            nbytes = lib.kd_bev_rasterize_ws_bytes(B, GH, GW)
+            if ws_holder[0] is None or ws_holder[0].numel() < nbytes:      # this stream's own claim table: ops.workspace()
+                ws_holder[0] = torch.empty(nbytes, dtype=torch.uint8, device="cuda")   # is the compute stream's
+            s = side.cuda_stream
+            lib.call("kd_bev_rasterize", P(x), P(y), P(cls), P(off), B, n, 1, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
+                     _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws_holder[0]), nbytes, P(seg), s)
+            lib.call("kd_points_prepare_batch", P(x), P(y), P(z), P(w), P(off), P(keys), B, n, self.max_points,
+                     int(sample_seed) & 0xFFFFFFFFFFFFFFFF, P(pts), s)
+            lib.call("kd_image_u8hwc_to_f32chw_batch", P(img8), P(img), B, H, W, s)
+        return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
+
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
         b = self.prepare_batch([self.load_raw(idx)])
         return {"image": b["image"][0], "points": b["points"][0], "segmentation": b["segmentation"][0],
@@ -181,7 +272,9 @@ class _RawFrames(Dataset):
         return len(self.ds)
 
     def __getitem__(self, idx):
-        return self.ds.load_raw(idx)
+        raw = self.ds.load_raw(idx)
+        raw["index"] = int(idx)                   # the dataset index: low word of the frame key of the device sampler
+        return raw
 
 
 class RankShardSampler(torch.utils.data.Sampler):
@@ -256,13 +349,28 @@ class _EpochLoader:
 class DeviceBatchLoader:
     """DataLoader over raw host frames (any num_workers) + per-batch device preparation in the consumer.
     With `world > 1` the frames are sharded over ranks (RankShardSampler); the training loader then also drops the
-    ragged last batch, so every rank runs the same number of steps."""
+    ragged last batch, so every rank runs the same number of steps.
+
+    `prefetch = 0`: each batch is prepared synchronously on the current stream between two steps (`prepare_batch`).
+    `prefetch >= 1`: that many prepared batches are kept in flight on a side stream, each with its own pinned staging
+    set (`prepare_batch_staged`), so batch k+1 is copied and prepared while the caller's step consumes batch k.  The
+    yielded tensors are safe on the caller's current stream as they are: that stream waits for the side stream's event
+    and the allocator is told of the cross-stream use.  Sweeps longer than max_points are then cut by the device sampler
+    under the frame key (epoch << 32) | dataset index and `sample_seed`: a frame gets a new subset every epoch
+    (`set_epoch`, else one epoch per `__iter__`) and the same one whenever (sample_seed, epoch, index) recur, on any
+    rank and in any batch."""
 
     def __init__(self, ds: PandaSetDataset, batch_size: int, shuffle: bool, num_workers: int, to_cpu: bool = False,
-                 rank: int = 0, world: int = 1, train: bool = None):
+                 rank: int = 0, world: int = 1, train: bool = None, prefetch: int = 0, sample_seed: int = 0):
+        if prefetch < 0:
+            raise KDError(f"prefetch must be >= 0, got {prefetch}")
         self.dataset = ds
         self.batch_size = batch_size
         self.to_cpu = to_cpu
+        self.prefetch, self.sample_seed = int(prefetch), int(sample_seed)
+        self._epoch, self._epoch_set = -1, None
+        self._side = self._staging = None
+        self._ws = [None]
         train = shuffle if train is None else train
         self._sampler = None
         if world > 1:
@@ -274,6 +382,7 @@ class DeviceBatchLoader:
                                       collate_fn=list)
 
     def set_epoch(self, epoch: int):
+        self._epoch_set = int(epoch)
         if self._sampler is not None:
             self._sampler.set_epoch(epoch)
 
@@ -281,12 +390,52 @@ class DeviceBatchLoader:
         return len(self._loader)
 
     def __iter__(self):
+        self._epoch, self._epoch_set = (self._epoch + 1 if self._epoch_set is None else self._epoch_set), None
         _collect_before_fork(self._loader)
+        if self.prefetch > 0:
+            yield from self._iter_prefetch(self._epoch)
+            return
         for raws in self._loader:
             b = self.dataset.prepare_batch(raws)
             if self.to_cpu:                 # for host-side analysis scripts that call .numpy() on the batch tensors
                 b = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in b.items()}
             yield b
+
+    def _deliver(self, item):
+        """Hand a batch prepared on the side stream to the caller's current stream."""
+        b, ready = item
+        cur = torch.cuda.current_stream()
+        cur.wait_event(ready)
+        for v in b.values():
+            if torch.is_tensor(v):
+                v.record_stream(cur)
+        if self.to_cpu:
+            b = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in b.items()}
+        return b
+
+    def _iter_prefetch(self, epoch: int):
+        if not torch.cuda.is_available():
+            raise KDError("input preparation runs on the MI355X; there is no CPU fallback")
+        if self._side is None:
+            self._side = torch.cuda.Stream()
+            self._staging = [StagingSet() for _ in range(self.prefetch)]
+        side, inflight, k = self._side, deque(), 0
+        try:
+            for raws in self._loader:
+                keys = [(epoch << 32) | (int(r["index"]) & 0xFFFFFFFF) for r in raws]
+                b = self.dataset.prepare_batch_staged(raws, self._staging[k % self.prefetch], side, keys, self.sample_seed, self._ws)
+                ready = torch.cuda.Event()
+                ready.record(side)
+                inflight.append((b, ready))
+                k += 1
+                if len(inflight) > self.prefetch:
+                    yield self._deliver(inflight.popleft())
+            while inflight:
+                yield self._deliver(inflight.popleft())
+        finally:
+            # left early (break, exception) or done: nothing stays pending on the side stream or in the staging sets
+            inflight.clear()
+            side.synchronize()
 
 
 class SyntheticPandaSet(Dataset):
@@ -309,20 +458,59 @@ class SyntheticPandaSet(Dataset):
                 "sample_token": f"synthetic_{i:06d}"}
 
 
+class SyntheticRawPandaSet(PandaSetDataset):
+    """In-memory raw source of the real shape, for measurement and tests without files: `load_raw(i)` returns a seeded
+    dictionary with an uint8 image, float32 x / y / z / i columns of a chosen sweep length and int64 raw class ids in
+    PandaSet's range (0..42).  `sweep_points`: one length or a sequence cycled over the frames (0 = an empty sweep);
+    `nan_frames`: indices whose first points get NaN coordinates; `unique`: frames i and i + unique share their arrays
+    (generated once and kept), so a long run does not time the generator."""
+
+    def __init__(self, n_frames: int = 64, sweep_points=169000, image_size: Tuple[int, int] = (256, 256),
+                 grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, seed: int = 0, nan_frames: Sequence[int] = (),
+                 unique: int = None):
+        self.root, self.scene_ids = None, []
+        self.image_size, self.grid_size, self.max_points = image_size, grid_size, max_points
+        self.pc_range = (-50, 50, -50, 50)
+        self.seed, self.nan_frames = seed, set(int(i) for i in nan_frames)
+        self.sweeps = [int(sweep_points)] if np.isscalar(sweep_points) else [int(v) for v in sweep_points]
+        self.unique = n_frames if unique is None else int(unique)
+        self.samples = [{"scene": "synthetic", "frame": f"{i:06d}"} for i in range(n_frames)]
+        self._made = {}
+
+    def load_raw(self, idx: int) -> Dict[str, object]:
+        u = idx % self.unique
+        if u not in self._made:
+            r = np.random.RandomState(self.seed * 100003 + u)
+            n = self.sweeps[u % len(self.sweeps)]
+            x, y = (r.randn(n) * 40.0).astype(np.float32), (r.randn(n) * 40.0).astype(np.float32)
+            z = (r.randn(n) * 4.0 - 1.0).astype(np.float32)
+            inten = r.randint(0, 256, n).astype(np.float32)
+            if u in self.nan_frames and n >= 2:
+                x[0], y[1] = np.nan, np.nan
+            self._made[u] = {"image_u8": r.randint(0, 256, (self.image_size[1], self.image_size[0], 3)).astype(np.uint8),
+                             "x": x, "y": y, "z": z, "i": inten, "class": r.randint(0, 43, n).astype(np.int64)}
+        return {**self._made[u], "sample_token": f"synthetic_{idx:06d}"}
+
+
 def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: List[str], batch_size: int = 4,
-                                num_workers: int = 0, verbose: bool = True, to_cpu: bool = None):
+                                num_workers: int = 0, verbose: bool = True, to_cpu: bool = None, prefetch: int = None):
     """Reference signature (pandaset_dataset.py:144-160) plus `to_cpu`: batches stay on the GPU by default (the trainers'
     `.to(device)` is then free); to_cpu=True (or KD_LOADER_TO_CPU=1) returns host tensors for the reference's analysis
-    scripts, which call `.numpy()` on them (test_dataset_distribution.py:22, verify_2class_distribution.py)."""
+    scripts, which call `.numpy()` on them (test_dataset_distribution.py:22, verify_2class_distribution.py).
+    `prefetch` (None: KD_LOADER_PREFETCH, default 0): batches prepared ahead of the step on a side stream, see
+    DeviceBatchLoader; KD_LOADER_SAMPLE_SEED seeds its device sampler."""
     if to_cpu is None:
         to_cpu = os.environ.get("KD_LOADER_TO_CPU") == "1"
+    if prefetch is None:
+        prefetch = int(os.environ.get("KD_LOADER_PREFETCH", "0"))
+    pf = {"prefetch": prefetch, "sample_seed": int(os.environ.get("KD_LOADER_SAMPLE_SEED", "0"))}
     # under torch.distributed (one process per GPU) the FRAMES are sharded over ranks, equal counts per rank for training
     rank, world = _dist_rank_world()
     if os.path.isdir(root):
         train_ds = PandaSetDataset(root, train_scenes, verbose=verbose)
         val_ds = PandaSetDataset(root, val_scenes, verbose=verbose)
-        return (DeviceBatchLoader(train_ds, batch_size, shuffle=True, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world),
-                DeviceBatchLoader(val_ds, batch_size, shuffle=False, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world))
+        return (DeviceBatchLoader(train_ds, batch_size, shuffle=True, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf),
+                DeviceBatchLoader(val_ds, batch_size, shuffle=False, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf))
     if verbose:
         print(f"[data] '{root}' not found: serving synthetic PandaSet-shaped frames")
     train = SyntheticPandaSet(n_frames=max(8, 8 * len(train_scenes)), seed=1)
