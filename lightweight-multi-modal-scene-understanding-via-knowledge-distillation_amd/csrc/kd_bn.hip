@@ -375,6 +375,7 @@ int kd_bn_bwd_reduce(const float* D, int64_t ldd, const float* X, int64_t ldx, c
                      int act, const float* mean, const float* invstd, float* partial, int64_t M, int C, void* stream) {
   KD_REQUIRE(D && X && mean && invstd && partial && M > 0 && C % 4 == 0 && C <= 1024, KD_ERR_ARG, "kd_bn_bwd_reduce: bad args");
   KD_REQUIRE(act == KD_ACT_NONE || (sc && sh), KD_ERR_ARG, "kd_bn_bwd_reduce: mask needs sc/sh");
+  KD_REQUIRE(ldd % 4 == 0 && ldx % 4 == 0, KD_ERR_SHAPE, "kd_bn_bwd_reduce: ld must be a multiple of 4");
   const KdCgLayout l = kd_cg_layout(M, C);
   BwdReduceArgs a{D, ldd, X, ldx, sc, sh, act, mean, invstd, partial, M, C, l.groups, l.slots};
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);

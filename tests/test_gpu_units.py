@@ -323,7 +323,8 @@ def test_inverted_residual_non_square(h, w, stride):
 def test_dw_stride1_backward_forms_agree(shape):
     """The three forms of the stride-1 depthwise backward (separate data / weight kernels, fused column walk, fused tile
     kernel staged through LDS) on odd and tile-crossing shapes: same data gradient bits (identical fma order), weight
-    gradient and BatchNorm-backward sums to rounding."""
+    gradient and BatchNorm-backward sums to rounding.  The forms share their operand helpers, so agreement is not truth:
+    every form is held to a float64 reference in tests/test_gpu_conv_kernels.py (test_dw_bwd_stride1_forms and the ladders)."""
     from kdrt.lib import lib
     from kdrt.ops import P, stream, workspace
     B, H, W, C = shape
@@ -411,7 +412,8 @@ def test_dw_backward_with_residual_addend(shape, deferred):
 def test_dw_stride2_backward_forms_agree(shape, deferred):
     """Stride-2 depthwise backward: separate data / weight kernels against the fused quad walk, on odd and even sizes,
     with a deferred (BatchNorm + ReLU6 on load) and a materialised input: same data gradient bits, weight gradient and
-    BatchNorm-backward sums to rounding."""
+    BatchNorm-backward sums to rounding.  The absolute check of both forms against float64 is
+    tests/test_gpu_conv_kernels.py::test_dw_bwd_stride2_forms (and the ladders there)."""
     from kdrt.lib import lib
     from kdrt.ops import P, stream, workspace
     B, H, W, C = shape
