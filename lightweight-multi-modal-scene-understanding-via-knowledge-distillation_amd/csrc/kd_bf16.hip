@@ -9,8 +9,10 @@
 // -- 8 consecutive bf16 of its row, 16 bytes -- straight from HBM as the MFMA operand; no conversion, no LDS for A.
 // Reference layers: camera_encoder.py:19-67, fusion_module.py:8-91,162-173, lidar_encoder.py:25-35,57-99.
 //
-// Accuracy is that of bf16 activations (8-bit mantissa): see tests/test_gpu_bf16.py for the measured logit error and the
-// argmax agreement with the fp32 path -- this mode is NOT part of the fp32 parity contract.
+// Accuracy is that of bf16 activations (8-bit mantissa): tests/test_gpu_bf16.py has the measured whole-model logit error and the
+// argmax agreement with the fp32 path; tests/test_gpu_bf16_kernels.py checks every entry point of this file on its own against a
+// float64 evaluation of the same bf16-rounded operands (bit for bit on exactly summable inputs, tests/_bf16_ref.py) -- this mode is
+// NOT part of the fp32 parity contract.
 #include "kd_common.h"
 
 #include <type_traits>
@@ -856,8 +858,9 @@ extern "C" {
 
 int kd_bf16_stem(const float* x_nchw, const float* w, const float* sc, const float* sh, int act, void* y, int B, int Cin, int H,
                  int W, int Cout, void* stream) {
-  KD_REQUIRE(x_nchw && w && sc && sh && y && B > 0 && Cin >= 1 && Cin <= 4, KD_ERR_ARG, "kd_bf16_stem: bad args");
+  KD_REQUIRE(x_nchw && w && sc && sh && y && B > 0 && Cin >= 1 && Cin <= 4 && H > 0 && W > 0, KD_ERR_ARG, "kd_bf16_stem: bad args");
   KD_REQUIRE(kd_stem_width_ok(Cout), KD_ERR_SHAPE, "kd_bf16_stem: only Cout in {8, 16, 24, 32, 40} (got %d)", Cout);
+  KD_REQUIRE(kd_aligned16(y), KD_ERR_ALIGN, "kd_bf16_stem: y must be 16-byte aligned (16-byte stores)");
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const int64_t npix = (int64_t)B * Ho * Wo;
   int64_t grid = (npix + 255) / 256;
@@ -873,7 +876,8 @@ int kd_bf16_stem(const float* x_nchw, const float* w, const float* sc, const flo
 
 int kd_bf16_dwconv3x3(const void* x, const float* w, const float* sc, const float* sh, int act, void* y, int B, int H, int W,
                       int C, int stride, void* stream) {
-  KD_REQUIRE(x && w && sc && sh && y && B > 0 && C % 8 == 0 && C <= 1024 && (stride == 1 || stride == 2), KD_ERR_ARG, "kd_bf16_dwconv3x3: bad args");
+  KD_REQUIRE(x && w && sc && sh && y && B > 0 && H > 0 && W > 0 && C >= 8 && C % 8 == 0 && C <= 1024 && (stride == 1 || stride == 2), KD_ERR_ARG,
+             "kd_bf16_dwconv3x3: bad args (B=%d H=%d W=%d C=%d stride=%d)", B, H, W, C, stride);
   KD_REQUIRE(kd_aligned16(x) && kd_aligned16(y), KD_ERR_ALIGN, "kd_bf16_dwconv3x3: alignment");
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   int groups, slots;
@@ -902,9 +906,15 @@ int kd_bf16_pwconv(const void* A, int64_t lda, int a_kind, const float* W, const
                    const int* cell, float* grid, int64_t ldgrid, void* stream) {
   KD_REQUIRE(A && W && esc && esh && M > 0 && K >= 8 && N >= 8, KD_ERR_ARG, "kd_bf16_pwconv: bad args");
   KD_REQUIRE(K % 8 == 0 && N % 8 == 0 && K <= 1024, KD_ERR_SHAPE, "kd_bf16_pwconv: K=%d and N=%d must be multiples of 8, K <= 1024", K, N);
-  KD_REQUIRE(a_kind == 3 || (lda % (a_kind == 0 ? 8 : 4) == 0 && kd_aligned16(A)), KD_ERR_ALIGN, "kd_bf16_pwconv: A alignment");
+  KD_REQUIRE(kd_aligned16(A) && (a_kind == 3 || lda % (a_kind == 0 ? 8 : 4) == 0), KD_ERR_ALIGN, "kd_bf16_pwconv: A alignment");
+  KD_REQUIRE(a_kind == 3 || lda >= K, KD_ERR_ARG, "kd_bf16_pwconv: lda=%lld is smaller than K=%d", (long long)lda, K);
   KD_REQUIRE(epi == 4 ? (cell && grid && (act == KD_ACT_RELU || act == KD_ACT_RELU6)) : (C != nullptr && ldc % 2 == 0 && (!res || ldres % 2 == 0)), KD_ERR_ARG,
              "kd_bf16_pwconv: epilogue arguments");
+  KD_REQUIRE(epi == 4 ? ldgrid >= N : (ldc >= N && (!res || ldres >= N)), KD_ERR_ARG, "kd_bf16_pwconv: a leading dimension of the output is smaller than N=%d",
+             N);
+  // C and res are stored / loaded as dwords (two bf16): even leading dimensions keep that aligned only from an aligned base
+  KD_REQUIRE(epi == 4 || ((reinterpret_cast<uintptr_t>(C) & 3u) == 0 && (reinterpret_cast<uintptr_t>(res) & 3u) == 0), KD_ERR_ALIGN,
+             "kd_bf16_pwconv: C and res must be 4-byte aligned");
   KD_REQUIRE(a_kind != 3 || (l0w && l0b && sc0 && sh0 && K % 4 == 0), KD_ERR_ARG, "kd_bf16_pwconv: layer-0 arguments");
   GemmBfArgs g{A, lda, W, bias, esc, esh, act, (bf16_t*)C, ldc, (const bf16_t*)res, ldres, M, K, N, m_dev, l0w, l0b, sc0, sh0, act0,
                cell, grid, ldgrid};
@@ -923,13 +933,17 @@ int kd_bf16_pwconv(const void* A, int64_t lda, int a_kind, const float* W, const
 
 int kd_bf16_bilinear_sum(const void* in0, int H0, int W0, const void* in1, int H1, int W1, const void* in2, int H2, int W2,
                          void* out, int B, int Ho, int Wo, int C, void* stream) {
-  KD_REQUIRE(in0 && out && B > 0 && C % 8 == 0 && C <= 2048, KD_ERR_ARG, "kd_bf16_bilinear_sum: bad args");
+  KD_REQUIRE(in0 && out && B > 0 && Ho > 0 && Wo > 0 && C >= 8 && C % 8 == 0 && C <= 2048, KD_ERR_ARG,
+             "kd_bf16_bilinear_sum: bad args (B=%d Ho=%d Wo=%d C=%d)", B, Ho, Wo, C);
+  KD_REQUIRE(kd_aligned16(out), KD_ERR_ALIGN, "kd_bf16_bilinear_sum: alignment of out");
   BlBfArgs a{};
   const void* ins[3] = {in0, in1, in2};
   const int hs[3] = {H0, H1, H2}, wsz[3] = {W0, W1, W2};
   a.nin = 0;
   for (int t = 0; t < 3; ++t)
     if (ins[t]) {
+      KD_REQUIRE(hs[t] > 0 && wsz[t] > 0, KD_ERR_ARG, "kd_bf16_bilinear_sum: input %d has size %d x %d", t, hs[t], wsz[t]);
+      KD_REQUIRE(kd_aligned16(ins[t]), KD_ERR_ALIGN, "kd_bf16_bilinear_sum: alignment of input %d", t);
       a.in[a.nin] = (const bf16_t*)ins[t]; a.Hi[a.nin] = hs[t]; a.Wi[a.nin] = wsz[t];
       a.sh[a.nin] = (float)hs[t] / (float)Ho; a.sw[a.nin] = (float)wsz[t] / (float)Wo;
       ++a.nin;
@@ -941,7 +955,9 @@ int kd_bf16_bilinear_sum(const void* in0, int H0, int W0, const void* in1, int H
 }
 
 int kd_bf16_cls_conv(const void* x, const float* w, const float* b, float* logits_nchw, int64_t M, int HW, int Cin, int NC, void* stream) {
-  KD_REQUIRE(x && w && b && logits_nchw && M > 0 && Cin % 8 == 0 && Cin <= 64 && NC >= 1 && NC <= 4, KD_ERR_ARG, "kd_bf16_cls_conv: bad args");
+  KD_REQUIRE(x && w && b && logits_nchw && M > 0 && HW > 0 && Cin >= 8 && Cin % 8 == 0 && Cin <= 64 && NC >= 1 && NC <= 4, KD_ERR_ARG,
+             "kd_bf16_cls_conv: bad args");
+  KD_REQUIRE(kd_aligned16(x), KD_ERR_ALIGN, "kd_bf16_cls_conv: x must be 16-byte aligned (16-byte loads)");
   int64_t grid = (M + 255) / 256;
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(cls_bf16_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, w, b, logits_nchw, M, HW, Cin, NC);
