@@ -416,6 +416,20 @@ int kd_dw_pw_infer(const float* x, const float* isc, const float* ish, int iact,
                    int dact, const float* wp, const float* pbias, const float* psc, const float* psh, int pact, const float* res,
                    int64_t ldres, float* out, int64_t ldo, int B, int H, int W, int Ch, int stride, int Cout, void* stream);
 
+/* The WHOLE InvertedResidual (expand 1x1 + BN + act, depthwise 3x3 + BN + act, project 1x1 + BN + act, + res) in one kernel: the 6x
+ * hidden tensor is neither written nor read.  The block-input halo tile of a workgroup is read once and kept as bf16x3 MFMA
+ * fragments; per 32 hidden channels the expand GEMM is recomputed over the 3x3 halo on the matrix pipe.
+ *   out[B*Ho*Wo, Cout] = pact(bn_p(conv1x1_p(dact(bn_d(dwconv3x3_stride(eact(bn_e(conv1x1_e(x) + ebias))))) + pbias)) (+ res)
+ * x: dense [B,H,W,Cin] NHWC of finished values, we: [Ch][Cin], ebias: [Ch] or NULL, esc / esh: [Ch] (required), the rest as
+ * kd_dw_pw_infer.  Split bf16x3 GEMM arithmetic; bit-identical to kd_pwconv_gemm(pro 0, epi 0) followed by kd_dw_pw_infer.
+ * Shapes (kd_block_infer_supported): Ch a multiple of 32 with (Cin 32, stride 2, Cout 64) or (Cin 64, stride 1, Cout 64);
+ * anything else returns KD_ERR_SHAPE. */
+int kd_block_infer_supported(int Cin, int Ch, int Cout, int stride);
+int kd_block_infer(const float* x, const float* we, const float* ebias, const float* esc, const float* esh, int eact, const float* wd,
+                   const float* dsc, const float* dsh, int dact, const float* wp, const float* pbias, const float* psc, const float* psh,
+                   int pact, const float* res, int64_t ldres, float* out, int64_t ldo, int B, int H, int W, int Cin, int Ch, int stride,
+                   int Cout, void* stream);
+
 /* ---- bf16-storage INFERENCE path (csrc/kd_bf16.hip; BASELINE.json configs[1]) -----------------------------------------
  * A second mode beside the fp32 contract: eval forward only.  Activations are bf16 NHWC matrices [M][C], already
  * normalised + activated; every entry point is one whole unit conv -> fma(raw, sc, sh) -> act (+ residual) -> bf16, with

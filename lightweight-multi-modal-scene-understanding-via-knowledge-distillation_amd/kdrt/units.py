@@ -270,8 +270,58 @@ def dw_pw_forward_final(dwu: UnitSpec, pwu: UnitSpec, inp: Operand, res: Optiona
     return out, (B, Ho, Wo)
 
 
+# A whole inference-mode InvertedResidual -- expand 1x1, depthwise 3x3, project 1x1 -- in one kernel (block_infer_kernel,
+# csrc/kd_block.hip): the 6x hidden tensor, which the expand GEMM otherwise writes and kd_dw_pw_infer reads straight back, never
+# exists; the expand is recomputed over the 3x3 halo from a register-resident input tile.  Same bits as the two launches.
+# BLOCK_INFER: 0 never, 1 by shape (the shapes that won the in-step A/B, profiles/block_infer_ab.txt), 2 every supported shape.
+BLOCK_INFER = [1]
+
+
+def block_infer_ok(units, cur) -> bool:
+    mode = BLOCK_INFER[0]
+    if mode == 0 or len(units) != 3 or [u.kind for u in units] != ["pw", "dw", "pw"]:
+        return False
+    if ops.get_gemm_arithmetic() != "split" or not isinstance(cur, Operand):
+        return False
+    if cur.bnc is not None or cur.raw is None or ld(cur.raw) != cur.C:     # a dense NHWC matrix of finished values
+        return False
+    eu, dwu, pwu = units
+    Ch, Cin = eu.conv.weight.shape[0], eu.conv.weight.shape[1]
+    Cout = pwu.conv.weight.shape[0]
+    if cur.C != Cin or dwu.conv.weight.shape[0] != Ch or pwu.conv.weight.shape[1] != Ch:
+        return False
+    if not lib.kd_block_infer_supported(Cin, Ch, Cout, dwu.stride):
+        return False
+    return mode >= 2 or (Cin, Ch, Cout, dwu.stride) in BLOCK_INFER_SHAPES
+
+
+# (Cin, Ch, Cout, stride) of the blocks that mode 1 sends to the one-kernel form: the teacher's stage 2 (expand GEMM + tail 1712 -> 1004 us
+# per launch at 256 frames) and stage 3 (1592 -> 1218 us), each more than five times the parent's launch-to-launch spread
+BLOCK_INFER_SHAPES = {(32, 192, 64, 2), (64, 384, 64, 1)}
+
+
+def block_forward_final(eu: UnitSpec, dwu: UnitSpec, pwu: UnitSpec, inp: Operand, res: Optional[torch.Tensor] = None):
+    """(1x1 + BN + act) -> (depthwise 3x3 + BN + act) -> (1x1 + BN + act) [+ residual] of an inference chain in one launch
+    -> (matrix, geom); the same bits as unit_forward(pw) followed by dw_pw_forward_final (tests/test_gpu_block_infer.py)."""
+    B, H, W = inp.geom
+    Cin, Ch, Cout = inp.C, eu.conv.weight.shape[0], pwu.conv.weight.shape[0]
+    s = dwu.stride
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    dev = inp.raw.device
+    be = _coeffs(eu, None, 0, Ch, inp.M, False, None, dev)
+    bd = _coeffs(dwu, None, 0, Ch, B * Ho * Wo, False, None, dev)
+    bp = _coeffs(pwu, None, 0, Cout, B * Ho * Wo, False, None, dev)
+    out = torch.empty(B * Ho * Wo, Cout, device=dev, dtype=torch.float32)
+    lib.call("kd_block_infer", P(inp.raw), P(eu.conv.weight), P(eu.conv.bias), P(be.scale), P(be.shift), eu.act, P(dwu.conv.weight),
+             P(bd.scale), P(bd.shift), dwu.act, P(pwu.conv.weight), P(pwu.conv.bias), P(bp.scale), P(bp.shift), pwu.act, P(res),
+             ld(res) if res is not None else 0, P(out), Cout, B, H, W, Cin, Ch, s, Cout, stream())
+    return out, (B, Ho, Wo)
+
+
 def infer_tail(units, cur, res: Optional[torch.Tensor] = None):
     """The units of an inference-mode chain whose last unit is a 1x1 conv -> (finished output matrix, geometry)."""
+    if block_infer_ok(units, cur):
+        return block_forward_final(units[0], units[1], units[2], cur, res)
     n_head = len(units) - 2
     if n_head >= 0:
         head = cur

@@ -15,7 +15,7 @@ tot = lambda sel: (sum(int(r["Calls"]) for r in rows if sel(r["Name"])), sum(flo
 fc, ft = tot(lambda n: "pw_gemm_kernel" in n or "pw_stream_kernel" in n)
 wc, wt = tot(lambda n: "pw_wgrad_kernel" in n)
 _, dt = tot(lambda n: "dw_" in n and "dw_pw_infer" not in n)
-_, zt = tot(lambda n: "dw_pw_infer" in n)
+_, zt = tot(lambda n: "dw_pw_infer" in n or "block_infer" in n)
 s = json.load(open(f"{E}/stats_bench.json"))
 r = s["roofline"]
 open(f"{ROOT}/profiles/r02_bench_kernel_summary_B256.txt", "w").write(f"""rocprofv3 --kernel-trace --stats of the default bench.py workload, round-2 final code (MI355X, ROCm 7.2)
@@ -25,7 +25,7 @@ bench.py line of the same run: {s['value']} frames/s, {s['ms_per_step']} ms/step
 forward / data-gradient GEMM family {r['avg_launch_us']} us over {r['launches_per_step']} launches per step.
 rocprof, same family (pw_gemm_kernel + pw_stream_kernel, all instances): {fc} calls, {ft / fc / 1e3:.1f} us average, {ft / 6e6:.2f} ms/step.
 weight-gradient GEMMs (pw_wgrad_kernel): {wc} calls, {wt / 6e6:.2f} ms/step.  depthwise kernels (dw_*): {dt / 6e6:.2f} ms/step (round 1: 16.4)
-+ {zt / 6e6:.2f} ms/step for the two fused inference tails (dw_pw_infer_kernel, which contain their 1x1 convolutions).
++ {zt / 6e6:.2f} ms/step for the fused inference tails (dw_pw_infer_kernel / block_infer_kernel, which contain their 1x1 convolutions).
 
 {summ}""")
 shutil.copy(f"{E}/stats/x/p_kernel_stats.csv", f"{ROOT}/profiles/r02_bench_kernel_stats_B256.csv")
