@@ -372,6 +372,20 @@ int kd_image_u8hwc_to_f32chw_batch(const uint8_t* in, float* out, int B, int H, 
 int kd_points_prepare_batch(const float* x, const float* y, const float* z, const float* intensity, const int64_t* offsets,
                             const uint64_t* frame_keys, int B, int64_t n_total, int64_t max_points, uint64_t seed, float* out,
                             void* stream);
+/* Pillow-exact 8-bit bilinear resize of a batch (pandaset_dataset.py:105-111): in[B,Hs,Ws,3] uint8 -> the bytes of
+ * Image.fromarray(frame).resize((W, H), Image.BILINEAR), written as out_f32chw[B,3,H,W] = byte / 255 (the bits of
+ * kd_image_u8hwc_to_f32chw_batch over the resized bytes) and / or out_u8hwc[B,H,W,3]; either output may be NULL, not both.
+ * Pillow's ImagingResample in integers: horizontal pass first, rounded to uint8, then the vertical pass over those bytes
+ * (kept in LDS); a sample is min(255, (2^21 + sum_t pixel[xmin + t] * k[t]) >> 22).  The tables are device pointers
+ * built by the host in double (kdrt/resample.py, mirrored by tests/_pil_resample_ref.py): hbounds int32 [W,2] =
+ * (xmin, n) per output column over the Ws axis, hk int32 [W,hks] its coefficients (n <= hks, tail ignored); vbounds
+ * [H,2] / vk [H,vks] the same over the Hs axis.  An axis whose size does not change takes the table of (in, in), which is
+ * the identity.  Supported (kd_image_resize_bilinear_supported, else KD_ERR_SHAPE and nothing is written): sources up
+ * to 4096 x 4096, any upscale, downscale up to a factor of 16 per axis (hks, vks <= 33).  No workspace, no atomics. */
+int kd_image_resize_bilinear_supported(int Hs, int Ws, int H, int W);
+int kd_image_resize_bilinear_batch(const uint8_t* in, const int32_t* hbounds, const int32_t* hk, int hks, const int32_t* vbounds,
+                                   const int32_t* vk, int vks, float* out_f32chw, uint8_t* out_u8hwc, int B, int Hs, int Ws,
+                                   int H, int W, void* stream);
 
 /* ---- losses, metric, optimiser (trainer.py:18-37,55-56,86-90; KD terms are build-defined) ------ */
 size_t kd_seg_loss_ws_bytes(int64_t npix);

@@ -13,6 +13,10 @@ consumes batch k: one host-to-device copy per tensor from pinned staging buffers
 (`prepare_batch_staged`) on a side stream; long sweeps are then cut by the device sampler of kd_points_prepare_batch,
 keyed on (`sample_seed`, epoch, dataset index).
 
+`device_resize=True` (opt-in, default off) moves the resize to the device as well: `load_raw` then only decodes, the
+full-size uint8 frames travel to the GPU and kd_image_resize_bilinear_batch produces the float32 [B,3,H,W] batch with
+Pillow's exact bytes (integer resample over host-built coefficient tables, kdrt/resample.py).
+
 `SyntheticPandaSet` serves frames of the same contract when there is no dataset on disk:
     image        float32 [3, 256, 256] in [0, 1]
     points       float32 [max_points, 4]  (x, y, z, intensity), zero-padded tail
@@ -30,6 +34,7 @@ from torch.utils.data import DataLoader, Dataset
 from kdrt import KDError
 from kdrt.lib import lib
 from kdrt.ops import P, stream, workspace
+from kdrt.resample import device_tables
 
 _DRIVABLE = {6, 7, 8, 9, 10, 12}          # Ground, Road, Lane markings, Stop lines, Other markings, Driveway (:13)
 _DRIVABLE_BITS = sum(1 << k for k in _DRIVABLE)
@@ -113,6 +118,33 @@ def image_to_chw(img_u8_hwc) -> torch.Tensor:
     return out
 
 
+def _resize_launch(src: torch.Tensor, size: Tuple[int, int], out_f32, out_u8, s: int):
+    """kd_image_resize_bilinear_batch over src uint8 [B,Hs,Ws,3] on stream `s`; size = (width, height) as Image.resize."""
+    B, Hs, Ws = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    W, H = int(size[0]), int(size[1])
+    if not lib.kd_image_resize_bilinear_supported(Hs, Ws, H, W):
+        raise KDError(f"device resize of {Ws}x{Hs} -> {W}x{H} (width x height) is outside the kernel's range: sources up to "
+                      "4096x4096, downscale up to a factor of 16 per axis")
+    hb, hk = device_tables(Ws, W, src.device)
+    vb, vk = device_tables(Hs, H, src.device)
+    lib.call("kd_image_resize_bilinear_batch", P(src), P(hb), P(hk), int(hk.shape[1]), P(vb), P(vk), int(vk.shape[1]),
+             P(out_f32), P(out_u8), B, Hs, Ws, H, W, s)
+
+
+def resize_images_pil_bilinear(img_u8_bhwc, size: Tuple[int, int], want_u8: bool = False):
+    """uint8 [B,Hs,Ws,3] frames of one size -> float32 [B,3,H,W] on the device, the bits of
+    `image_to_chw(Image.fromarray(frame).resize(size, Image.BILINEAR))` per frame; size = (width, height) as Pillow takes
+    it.  want_u8=True also returns the resized bytes, uint8 [B,H,W,3]."""
+    t = _dev(img_u8_bhwc if torch.is_tensor(img_u8_bhwc) else np.asarray(img_u8_bhwc), torch.uint8)
+    if t.dim() != 4 or t.shape[3] != 3 or t.shape[0] == 0:
+        raise KDError(f"expected B x H x W x 3 uint8 images, got {tuple(t.shape)}")
+    W, H = int(size[0]), int(size[1])
+    out = torch.empty(t.shape[0], 3, H, W, dtype=torch.float32, device="cuda")
+    u8 = torch.empty(t.shape[0], H, W, 3, dtype=torch.uint8, device="cuda") if want_u8 else None
+    _resize_launch(t, (W, H), out, u8, stream())
+    return (out, u8) if want_u8 else out
+
+
 class StagingSet:
     """Pinned host buffers of ONE batch in flight (grow-only) + the event after its host-to-device copies: the buffers
     are not refilled before that event has completed."""
@@ -147,7 +179,7 @@ class StagingSet:
             raise KDError(f"expected HxWx3 uint8 images of one size per batch, got {[np.shape(r['image_u8']) for r in raws]}")
         img = self._fit("img", B * shape[0] * shape[1] * 3, torch.uint8)[: B * shape[0] * shape[1] * 3].reshape(B, *shape)
         for b, r in enumerate(raws):
-            img[b] = r["image_u8"]
+            img[b] = np.asarray(r["image_u8"])
         meta = self._fit("meta", 2 * B + 1, torch.int64)
         meta[0] = 0
         np.cumsum(lens, out=meta[1:B + 1])
@@ -159,9 +191,11 @@ class PandaSetDataset(Dataset):
     """2-class version: background (0) and drivable (1, includes lanes)."""
 
     def __init__(self, root: str, scene_ids: List[str], image_size: Tuple[int, int] = (256, 256),
-                 grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, verbose: bool = True):
+                 grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, verbose: bool = True,
+                 device_resize: bool = False):
         self.root, self.scene_ids = root, scene_ids
         self.image_size, self.grid_size, self.max_points = image_size, grid_size, max_points
+        self.device_resize = bool(device_resize)
         self.pc_range = (-50, 50, -50, 50)
         self.samples = self._index_scenes(verbose=verbose)
         if verbose:
@@ -192,15 +226,27 @@ class PandaSetDataset(Dataset):
 
     def load_raw(self, idx: int) -> Dict[str, object]:
         """Host I/O only (safe in DataLoader workers): decoded + resized uint8 image, float32 point columns,
-        int64 raw class ids."""
+        int64 raw class ids.  With `device_resize` the image is the decoded full-size frame as a torch.uint8 tensor
+        (DataLoader workers hand tensors over through shared memory; the resize happens in prepare_batch*)."""
         import pandas as pd
         from PIL import Image
         s = self.samples[idx]
-        img = Image.open(s["image"]).convert("RGB").resize(self.image_size, Image.BILINEAR)
+        img = Image.open(s["image"]).convert("RGB")
+        img = torch.from_numpy(np.array(img)) if self.device_resize else img.resize(self.image_size, Image.BILINEAR)
         lidar = pd.read_pickle(s["lidar"])
         cols = {c: lidar[c].to_numpy(dtype=np.float32) for c in ("x", "y", "z", "i")}
         raw_ids = pd.read_pickle(s["semseg"])["class"].to_numpy(dtype=np.int64)
-        return {"image_u8": np.asarray(img), **cols, "class": raw_ids, "sample_token": f"{s['scene']}_{s['frame']}"}
+        return {"image_u8": img if self.device_resize else np.asarray(img), **cols, "class": raw_ids,
+                "sample_token": f"{s['scene']}_{s['frame']}"}
+
+    def _needs_resize(self, shape) -> bool:
+        """A frame of (height, width) = shape[:2] goes through the device resize: opted in and not yet image_size."""
+        return self.device_resize and (int(shape[1]), int(shape[0])) != (int(self.image_size[0]), int(self.image_size[1]))
+
+    def _image_chw(self, img_u8) -> torch.Tensor:
+        if self._needs_resize(np.shape(img_u8)):
+            return resize_images_pil_bilinear(img_u8[None], self.image_size)[0]
+        return image_to_chw(img_u8)
 
     def prepare_batch(self, raws: Sequence[Dict[str, object]]) -> Dict[str, object]:
         """Device stage for a list of `load_raw` results -> the collated batch the trainers consume."""
@@ -208,14 +254,15 @@ class PandaSetDataset(Dataset):
         ys = [_dev(r["y"], torch.float32) for r in raws]
         seg = rasterize_bev_batch(xs, ys, [r["class"] for r in raws], self.grid_size, self.pc_range, remap=True)
         pts = torch.stack([prepare_points(x, y, r["z"], r["i"], self.max_points) for x, y, r in zip(xs, ys, raws)])
-        img = torch.stack([image_to_chw(r["image_u8"]) for r in raws])
+        img = torch.stack([self._image_chw(r["image_u8"]) for r in raws])
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
 
     def prepare_batch_staged(self, raws: Sequence[Dict[str, object]], staging: StagingSet, side: "torch.cuda.Stream",
                              frame_keys: Sequence[int], sample_seed: int = 0, ws_holder: list = None) -> Dict[str, object]:
         """`prepare_batch` for a whole batch at once, enqueued on the stream `side`: one host-to-device copy per tensor
         from the pinned `staging` set (packed point columns, class ids, uint8 images, offsets + frame keys), then three
-        launches (rasteriser, batched points, batched images).  Sweeps longer than max_points are cut by the device
+        launches (rasteriser, batched points, batched images -- with `device_resize` and full-size frames the image
+        launch is the Pillow-exact resize).  Sweeps longer than max_points are cut by the device
         sampler of kd_points_prepare_batch under (`sample_seed`, frame key).  The tensors returned belong to `side`:
         a consumer on another stream waits for an event recorded after this call and tells the allocator
         (`record_stream`).  `ws_holder`: a one-element list that keeps the rasteriser's workspace of this stream."""
@@ -244,7 +291,9 @@ class PandaSetDataset(Dataset):
             off, keys = meta[:B + 1], meta[B + 1:]
             seg = torch.empty(B, GH, GW, dtype=torch.int64, device="cuda")
             pts = torch.empty(B, self.max_points, 4, dtype=torch.float32, device="cuda")
-            img = torch.empty(B, 3, H, W, dtype=torch.float32, device="cuda")
+            resize = self._needs_resize((H, W))
+            OW, OH = (int(self.image_size[0]), int(self.image_size[1])) if resize else (W, H)
+            img = torch.empty(B, 3, OH, OW, dtype=torch.float32, device="cuda")
             nbytes = lib.kd_bev_rasterize_ws_bytes(B, GH, GW)
             if ws_holder[0] is None or ws_holder[0].numel() < nbytes:      # this stream's own claim table: ops.workspace()
                 ws_holder[0] = torch.empty(nbytes, dtype=torch.uint8, device="cuda")   # is the compute stream's
@@ -253,7 +302,10 @@ class PandaSetDataset(Dataset):
                      _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws_holder[0]), nbytes, P(seg), s)
             lib.call("kd_points_prepare_batch", P(x), P(y), P(z), P(w), P(off), P(keys), B, n, self.max_points,
                      int(sample_seed) & 0xFFFFFFFFFFFFFFFF, P(pts), s)
-            lib.call("kd_image_u8hwc_to_f32chw_batch", P(img8), P(img), B, H, W, s)
+            if resize:
+                _resize_launch(img8, (OW, OH), img, None, s)
+            else:
+                lib.call("kd_image_u8hwc_to_f32chw_batch", P(img8), P(img), B, H, W, s)
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
 
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
@@ -358,12 +410,19 @@ class DeviceBatchLoader:
     and the allocator is told of the cross-stream use.  Sweeps longer than max_points are then cut by the device sampler
     under the frame key (epoch << 32) | dataset index and `sample_seed`: a frame gets a new subset every epoch
     (`set_epoch`, else one epoch per `__iter__`) and the same one whenever (sample_seed, epoch, index) recur, on any
-    rank and in any batch."""
+    rank and in any batch.
+
+    `device_resize` (None: the dataset's own setting): the workers only decode and the full-size uint8 frames are
+    resized on the device (kd_image_resize_bilinear_batch, Pillow's bytes); the pinned staging set then holds the
+    full-size frames of a batch (6.2 MB per 1920x1080 frame)."""
 
     def __init__(self, ds: PandaSetDataset, batch_size: int, shuffle: bool, num_workers: int, to_cpu: bool = False,
-                 rank: int = 0, world: int = 1, train: bool = None, prefetch: int = 0, sample_seed: int = 0):
+                 rank: int = 0, world: int = 1, train: bool = None, prefetch: int = 0, sample_seed: int = 0,
+                 device_resize: bool = None):
         if prefetch < 0:
             raise KDError(f"prefetch must be >= 0, got {prefetch}")
+        if device_resize is not None:            # None: as the dataset was built; the workers' load_raw reads the flag
+            ds.device_resize = bool(device_resize)
         self.dataset = ds
         self.batch_size = batch_size
         self.to_cpu = to_cpu
@@ -463,13 +522,16 @@ class SyntheticRawPandaSet(PandaSetDataset):
     dictionary with an uint8 image, float32 x / y / z / i columns of a chosen sweep length and int64 raw class ids in
     PandaSet's range (0..42).  `sweep_points`: one length or a sequence cycled over the frames (0 = an empty sweep);
     `nan_frames`: indices whose first points get NaN coordinates; `unique`: frames i and i + unique share their arrays
-    (generated once and kept), so a long run does not time the generator."""
+    (generated once and kept), so a long run does not time the generator.  `source_size` (width, height; None: frames are
+    born at image_size, as before): the camera frame is generated at that size, and `load_raw` serves it whole as a
+    torch.uint8 tensor under `device_resize`, else resized on the host by Pillow as the real reader does."""
 
     def __init__(self, n_frames: int = 64, sweep_points=169000, image_size: Tuple[int, int] = (256, 256),
                  grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, seed: int = 0, nan_frames: Sequence[int] = (),
-                 unique: int = None):
+                 unique: int = None, source_size: Tuple[int, int] = None, device_resize: bool = False):
         self.root, self.scene_ids = None, []
         self.image_size, self.grid_size, self.max_points = image_size, grid_size, max_points
+        self.source_size, self.device_resize = source_size, bool(device_resize)
         self.pc_range = (-50, 50, -50, 50)
         self.seed, self.nan_frames = seed, set(int(i) for i in nan_frames)
         self.sweeps = [int(sweep_points)] if np.isscalar(sweep_points) else [int(v) for v in sweep_points]
@@ -487,28 +549,40 @@ class SyntheticRawPandaSet(PandaSetDataset):
             inten = r.randint(0, 256, n).astype(np.float32)
             if u in self.nan_frames and n >= 2:
                 x[0], y[1] = np.nan, np.nan
-            self._made[u] = {"image_u8": r.randint(0, 256, (self.image_size[1], self.image_size[0], 3)).astype(np.uint8),
+            fw, fh = self.image_size if self.source_size is None else self.source_size
+            self._made[u] = {"image_u8": r.randint(0, 256, (fh, fw, 3)).astype(np.uint8),
                              "x": x, "y": y, "z": z, "i": inten, "class": r.randint(0, 43, n).astype(np.int64)}
-        return {**self._made[u], "sample_token": f"synthetic_{idx:06d}"}
+        raw = {**self._made[u], "sample_token": f"synthetic_{idx:06d}"}
+        if self.source_size is not None:
+            if self.device_resize:
+                raw["image_u8"] = torch.from_numpy(raw["image_u8"])
+            else:
+                from PIL import Image
+                raw["image_u8"] = np.asarray(Image.fromarray(raw["image_u8"]).resize(self.image_size, Image.BILINEAR))
+        return raw
 
 
 def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: List[str], batch_size: int = 4,
-                                num_workers: int = 0, verbose: bool = True, to_cpu: bool = None, prefetch: int = None):
+                                num_workers: int = 0, verbose: bool = True, to_cpu: bool = None, prefetch: int = None,
+                                device_resize: bool = None):
     """Reference signature (pandaset_dataset.py:144-160) plus `to_cpu`: batches stay on the GPU by default (the trainers'
     `.to(device)` is then free); to_cpu=True (or KD_LOADER_TO_CPU=1) returns host tensors for the reference's analysis
     scripts, which call `.numpy()` on them (test_dataset_distribution.py:22, verify_2class_distribution.py).
     `prefetch` (None: KD_LOADER_PREFETCH, default 0): batches prepared ahead of the step on a side stream, see
-    DeviceBatchLoader; KD_LOADER_SAMPLE_SEED seeds its device sampler."""
+    DeviceBatchLoader; KD_LOADER_SAMPLE_SEED seeds its device sampler.  `device_resize` (None: KD_LOADER_DEVICE_RESIZE=1,
+    default off): the workers only decode and the bilinear resize runs on the device with Pillow's bytes."""
     if to_cpu is None:
         to_cpu = os.environ.get("KD_LOADER_TO_CPU") == "1"
     if prefetch is None:
         prefetch = int(os.environ.get("KD_LOADER_PREFETCH", "0"))
+    if device_resize is None:
+        device_resize = os.environ.get("KD_LOADER_DEVICE_RESIZE") == "1"
     pf = {"prefetch": prefetch, "sample_seed": int(os.environ.get("KD_LOADER_SAMPLE_SEED", "0"))}
     # under torch.distributed (one process per GPU) the FRAMES are sharded over ranks, equal counts per rank for training
     rank, world = _dist_rank_world()
     if os.path.isdir(root):
-        train_ds = PandaSetDataset(root, train_scenes, verbose=verbose)
-        val_ds = PandaSetDataset(root, val_scenes, verbose=verbose)
+        train_ds = PandaSetDataset(root, train_scenes, verbose=verbose, device_resize=device_resize)
+        val_ds = PandaSetDataset(root, val_scenes, verbose=verbose, device_resize=device_resize)
         return (DeviceBatchLoader(train_ds, batch_size, shuffle=True, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf),
                 DeviceBatchLoader(val_ds, batch_size, shuffle=False, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf))
     if verbose:

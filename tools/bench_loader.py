@@ -11,12 +11,19 @@ time per step = their difference, and beside it the compute stream's idle gap be
 recorded on it around the loader's `next()` (before: after the last kernel of the previous step; after: once the batch
 is usable).  The rounds alternate the configurations; the spread over rounds is the table's own noise figure.
 
+`--device-resize` adds, per prefetch depth, the same loop over full-size camera frames (`--source-size`, 1920x1080) that
+the device resizes (kd_image_resize_bilinear_batch, `device_resize=True`), alternating with the default path in every
+round, and two sections of its own: the per-launch time of the resize kernel (HIP events around back-to-back launches)
+with the HBM bytes it implies, and the host milliseconds per frame of `PandaSetDataset.load_raw` over JPEGs of that
+size written to a temporary directory, with and without the host resize.
+
   ref   : B = 4,   169 000-point sweeps, max_points = 5 000   (the reference's own shape)
   bench : B = 256, 169 000-point sweeps, max_points = 80 000  (the benchmarked shape; weighted student, concat teacher)
 """
 import argparse
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +49,12 @@ def run_shape(name, args, out):
     ds = SyntheticRawPandaSet(n_frames=B * n_batches, sweep_points=sweep, max_points=max_points, unique=min(B, 64), seed=1)
     for u in range(ds.unique):
         ds.load_raw(u)                                                       # generate once, outside every timed window
+    ds_full = None
+    if args.device_resize:                                                   # same sweeps, full-size frames, resized on the device
+        ds_full = SyntheticRawPandaSet(n_frames=B * n_batches, sweep_points=sweep, max_points=max_points, unique=min(B, 64), seed=1,
+                                       source_size=args.source_size, device_resize=True)
+        for u in range(ds_full.unique):
+            ds_full.load_raw(u)
 
     def resident():
         b = next(iter(DeviceBatchLoader(ds, B, shuffle=False, num_workers=0, prefetch=0)))
@@ -55,8 +68,8 @@ def run_shape(name, args, out):
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / args.steps * 1e3
 
-    def fed(prefetch):
-        loader = DeviceBatchLoader(ds, B, shuffle=False, num_workers=0, prefetch=prefetch, sample_seed=1)
+    def fed(prefetch, src=None):
+        loader = DeviceBatchLoader(src or ds, B, shuffle=False, num_workers=0, prefetch=prefetch, sample_seed=1)
         it, gaps, t0, t_host = iter(loader), [], None, 0.0
         for k in range(n_batches):
             if k == args.warmup:
@@ -83,6 +96,8 @@ def run_shape(name, args, out):
         rows.setdefault("resident", []).append((resident(), 0.0, 0.0))
         for p in args.prefetch:
             rows.setdefault(f"prefetch={p}", []).append(fed(p))
+            if ds_full is not None:
+                rows.setdefault(f"prefetch={p}+dr", []).append(fed(p, ds_full))
     res = [r[0] for r in rows["resident"]]
     res_ms = sum(res) / len(res)
     out.append(f"shape {name}: B = {B}, {sweep}-point sweeps, max_points = {max_points}; {args.steps} timed steps after {args.warmup} "
@@ -90,13 +105,79 @@ def run_shape(name, args, out):
     out.append(f"  {'configuration':<14}{'ms/step':>34}{'exposed = fed - resident':>28}{'stream gap (HIP events)':>34}{'host ms in next()':>28}")
     fmt = lambda vs: " ".join(f"{v:9.2f}" for v in vs) + f" |{sum(vs) / len(vs):9.2f}"
     out.append(f"  {'resident':<14}{fmt(res):>34}")
-    for p in args.prefetch:
-        r = rows[f"prefetch={p}"]
-        out.append(f"  {'prefetch=' + str(p):<14}{fmt([v[0] for v in r]):>34}{fmt([v[0] - res_ms for v in r]):>28}"
+    for key in [k for p in args.prefetch for k in (f"prefetch={p}", f"prefetch={p}+dr") if k in rows]:
+        r = rows[key]
+        out.append(f"  {key:<14}{fmt([v[0] for v in r]):>34}{fmt([v[0] - res_ms for v in r]):>28}"
                    f"{fmt([v[1] for v in r]):>34}{fmt([v[2] for v in r]):>28}")
     out.append("")
     del step, opt, teacher, student
     torch.cuda.empty_cache()
+
+
+def resize_kernel_section(args, out):
+    """Per-launch time of kd_image_resize_bilinear_batch from `--source-size` to 256x256 (float output only, as the loader
+    calls it) next to kd_image_u8hwc_to_f32chw_batch over already-resized frames; bytes = what each must move."""
+    from kdrt.lib import lib
+    from kdrt.ops import P, stream
+    from src.data_loading.pandaset_dataset import _resize_launch
+    Ws, Hs = args.source_size
+    out.append(f"resize kernel, {Ws}x{Hs} -> 256x256, HIP events around {args.kernel_reps} back-to-back launches after 3 warm-up launches")
+    out.append(f"  {'B':>5}{'us/launch':>12}{'MB read+written':>18}{'GB/s':>9}{'   | u8->f32 batch kernel on 256x256 frames: us/launch':<40}")
+    for B in (4, 256):
+        src = torch.randint(0, 256, (B, Hs, Ws, 3), dtype=torch.uint8, device="cuda")
+        small = torch.randint(0, 256, (B, 256, 256, 3), dtype=torch.uint8, device="cuda")
+        dst = torch.empty(B, 3, 256, 256, dtype=torch.float32, device="cuda")
+        runs = {"resize": lambda: _resize_launch(src, (256, 256), dst, None, stream()),
+                "chw": lambda: lib.call("kd_image_u8hwc_to_f32chw_batch", P(small), P(dst), B, 256, 256, stream())}
+        us = {}
+        for name, fn in runs.items():
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.kernel_reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us[name] = e0.elapsed_time(e1) / args.kernel_reps * 1e3
+        mb = (src.numel() + dst.numel() * 4) / 1e6
+        out.append(f"  {B:>5}{us['resize']:>12.1f}{mb:>18.1f}{mb / us['resize'] * 1e3:>9.0f}   | {us['chw']:.1f}")
+        del src, small, dst
+    out.append("")
+    torch.cuda.empty_cache()
+
+
+def load_raw_section(args, out):
+    """Host ms per frame in PandaSetDataset.load_raw over `--source-size` JPEGs (one process, one frame at a time)."""
+    import numpy as np
+    import pandas as pd
+    from PIL import Image
+    from src.data_loading.pandaset_dataset import PandaSetDataset
+    Ws, Hs = args.source_size
+    n = 6
+    with tempfile.TemporaryDirectory() as root:
+        dirs = [os.path.join(root, "001", *p) for p in (("camera", "front_camera"), ("lidar",), ("annotations", "semseg"))]
+        for d in dirs:
+            os.makedirs(d)
+        r = np.random.RandomState(0)
+        yy, xx = np.mgrid[:Hs, :Ws]
+        for k in range(n):                                                   # smooth content + mild noise, as a photograph compresses
+            base = np.stack([127 + 120 * np.sin(xx / (37.0 + 5 * c + k) + yy / (53.0 + 3 * c)) for c in range(3)], axis=2)
+            img = np.clip(base + r.randn(Hs, Ws, 3) * 6.0, 0, 255).astype(np.uint8)
+            Image.fromarray(img).save(os.path.join(dirs[0], f"{k:02d}.jpg"), quality=90)
+            pd.DataFrame({c: r.randn(1000) for c in "xyzi"}).to_pickle(os.path.join(dirs[1], f"{k:02d}.pkl"))
+            pd.DataFrame({"class": r.randint(0, 43, 1000)}).to_pickle(os.path.join(dirs[2], f"{k:02d}.pkl"))
+        out.append(f"host ms per frame in load_raw, {n} JPEGs of {Ws}x{Hs} (quality 90) + 1000-point pickles, one process, 3 passes (first = warm-up)")
+        for flag in (False, True):
+            ds = PandaSetDataset(root, ["001"], verbose=False, device_resize=flag)
+            per = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                for i in range(n):
+                    ds.load_raw(i)
+                per.append((time.perf_counter() - t0) / n * 1e3)
+            out.append(f"  device_resize={str(flag):<6} {per[1]:8.2f} {per[2]:8.2f}   ({'decode only' if flag else 'decode + Pillow resize to 256x256'})")
+    out.append("")
 
 
 def main():
@@ -106,14 +187,22 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--device-resize", action="store_true", help="add the device_resize=True loop over full-size frames and its sections")
+    ap.add_argument("--source-size", default="1920x1080", help="WIDTHxHEIGHT of the full-size camera frames")
+    ap.add_argument("--kernel-reps", type=int, default=20)
     ap.add_argument("--out", default=None, help="also write the table to this file")
     args = ap.parse_args()
     args.prefetch = [int(v) for v in args.prefetch.split(",")]
+    args.source_size = tuple(int(v) for v in args.source_size.split("x"))
     if not torch.cuda.is_available():
         raise SystemExit("bench_loader.py needs an MI355X: the product path has no CPU fallback")
     out = ["KD step fed by DeviceBatchLoader over SyntheticRawPandaSet (decode and unpickle excluded: raw frames served from memory)",
            f"device: {torch.cuda.get_device_name(0)}; concat teacher -> weighted student, image 3x256x256, BEV 64x64; times in ms", ""]
-    for name in args.shapes.split(","):
+    if args.device_resize:
+        out.insert(2, f"rows `+dr`: {args.source_size[0]}x{args.source_size[1]} frames from memory, resized on the device (device_resize=True)")
+        resize_kernel_section(args, out)
+        load_raw_section(args, out)
+    for name in [v for v in args.shapes.split(",") if v]:
         run_shape(name, args, out)
     text = "\n".join(out)
     print(text, flush=True)
