@@ -416,6 +416,34 @@ int kd_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float
  * advances state[1] on the device and refreshes the bias corrections before the update. */
 int kd_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, float beta1,
                       float beta2, float eps, float weight_decay, float ginv, void* stream);
+/* Global-norm gradient clipping on the device.
+ * kd_grad_sumsq_partials: ws[b] (double) = the sum of g[i]^2 over the elements block b of the launch owns, for
+ * b < kd_grad_sumsq_ws_bytes(n) / 8.  256 threads, one float4 per thread and iteration, at most 2048 blocks; fp32 inside a thread
+ * and a wave, double from there on; fixed summation order, no atomics: the same input gives the same bits on every run and on
+ * every replay of a captured graph.  n must be a positive multiple of 4 (KD_ERR_ARG; pad with zeros, as the flat gradient buffer
+ * of kdrt.optim.FlatParams is), g 16-byte and ws 8-byte aligned (KD_ERR_ALIGN), ws_bytes >= kd_grad_sumsq_ws_bytes(n)
+ * (KD_ERR_WORKSPACE).  A refused call launches nothing.
+ *
+ * kd_adamw_step_clip_dev: kd_adamw_step_dev with the gradient clipped to a global L2 norm of max_norm.  `state` is the same
+ * float[4]; `clip_state` is a second device float[4] {grad_norm, gscale, skipped_steps, last_step_finite}, of which the caller
+ * zeroes skipped_steps once.  Three launches (partials, a one-block tick, the update), no host synchronisation:
+ *   grad_norm = ginv * sqrt(sum g^2)         the norm of the gradient the optimiser applies (the rank average when ginv = 1/world)
+ *   clip_coef = min(1, max_norm / (grad_norm + 1e-6))                       torch.nn.utils.clip_grad_norm_'s formula, in fp32
+ *   gscale    = ginv * clip_coef             one fp32 product: bit-equal to ginv when nothing is clipped, and the update is then
+ *                                            bit-identical to kd_adamw_step_dev's
+ * and the update uses g[i] * gscale where kd_adamw_step_dev uses g[i] * ginv.  g itself is only read: after the call it still
+ * holds the unclipped gradients (under data parallelism the summed ones).
+ * A non-finite grad_norm (an inf or NaN anywhere in g, or a sum of squares beyond the fp32 range) SKIPS the step: p, m, v and
+ * state keep their bits -- the step count does not advance --, skipped_steps goes up by one, last_step_finite is 0, gscale is 0
+ * and grad_norm holds the non-finite value.  This departs on purpose from clip_grad_norm_(error_if_nonfinite=False), which would
+ * scale by NaN and leave NaN in every parameter.
+ * max_norm must be finite and > 0, n a positive multiple of 4 (KD_ERR_ARG); p, g, m, v 16-byte and ws 8-byte aligned
+ * (KD_ERR_ALIGN); ws_bytes >= kd_grad_sumsq_ws_bytes(n) (KD_ERR_WORKSPACE).  A refused call launches nothing. */
+size_t kd_grad_sumsq_ws_bytes(int64_t n);
+int kd_grad_sumsq_partials(const float* g, int64_t n, void* ws, size_t ws_bytes, void* stream);
+int kd_adamw_step_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, float* clip_state, void* ws,
+                           size_t ws_bytes, float beta1, float beta2, float eps, float weight_decay, float ginv, float max_norm,
+                           void* stream);
 
 /* ---- inference-mode block fusion (csrc/kd_block.hip) ------------------------------------------------------------------
  * The tail of an InvertedResidual (reference camera_encoder.py:30-42: depthwise 3x3 + BN + ReLU6, project 1x1 + BN, + x) or a

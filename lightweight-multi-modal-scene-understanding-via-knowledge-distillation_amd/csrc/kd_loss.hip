@@ -356,3 +356,135 @@ int kd_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, f
 }
 
 }  // extern "C"
+
+// ---- global-norm gradient clipping folded into the device-state AdamW step ------------------------------------------------
+// Launch layout of the sum of squares (mirrored by tests/_fp64_clip_ref.py): 256 threads, one float4 per thread and iteration,
+// at most GSQ_CAP blocks.  A thread adds its squares in fp32 (one fused multiply-add per element), a wave adds its 64 lanes in
+// fp32 (6 butterfly steps), everything after that is double: the 4 waves of a block, the per-block partials, the final sum.
+// No atomics and a fixed order everywhere, so the same input gives the same bits on every run and every graph replay.
+namespace {
+
+constexpr int GSQ_CAP = 2048;
+
+inline int64_t gsq_blocks(int64_t n) {
+  int64_t g = (n / 4 + 255) / 256;
+  return g > GSQ_CAP ? GSQ_CAP : (g < 1 ? 1 : g);
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, int64_t n4, double* partial) {
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 x = kd_ld4(g + i * 4);
+    s = fmaf(x.x, x.x, fmaf(x.y, x.y, fmaf(x.z, x.z, fmaf(x.w, x.w, s))));
+  }
+  __shared__ float red[4];
+  s = kd_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (((double)red[0] + (double)red[1]) + (double)red[2]) + (double)red[3];
+}
+
+// One block.  Sums the partials (thread t takes t, t + 256, ...; then a halving tree over the 256 threads), forms the norm, the
+// clip coefficient and the gradient scale, and advances the AdamW state only when the norm is finite.
+//   clip[0] = grad_norm = ginv * sqrt(sum)  (evaluated in double, rounded once)
+//   clip[1] = gscale = ginv * min(1, max_norm / (grad_norm + 1e-6))  (fp32 operations, torch.nn.utils.clip_grad_norm_'s formula)
+//   clip[2] = skipped steps (counts up on a non-finite norm)      clip[3] = 1 if this step is applied, 0 if it is skipped
+__global__ __launch_bounds__(256) void adamw_clip_tick_kernel(const double* partial, int nblk, float* state, float* clip, float b1,
+                                                              float b2, float ginv, float max_norm) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)((double)ginv * sqrt(red[0]));
+    clip[0] = norm;
+    if (isfinite(norm)) {
+      const float coef = fminf(1.f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)));
+      clip[1] = __fmul_rn(ginv, coef);
+      clip[3] = 1.f;
+      const float t = state[1] + 1.f;              // adamw_tick_kernel
+      state[1] = t;
+      state[2] = (float)(1.0 - pow((double)b1, (double)t));
+      state[3] = (float)sqrt(1.0 - pow((double)b2, (double)t));
+    } else {
+      clip[1] = 0.f;
+      clip[2] = clip[2] + 1.f;
+      clip[3] = 0.f;
+    }
+  }
+}
+
+// adamw_dev_kernel's arithmetic, expression for expression, on one element with the gradient scale read from the device
+__device__ __forceinline__ void adamw_clip_elem(float& p, float g, float& m, float& v, float lr, float bc1, float bc2sqrt, float b1,
+                                                float b2, float eps, float wd, float gs) {
+  const float gi = g * gs;
+  float pi = p * (1.f - lr * wd);
+  const float mi = b1 * m + (1.f - b1) * gi;
+  const float vi = b2 * v + (1.f - b2) * gi * gi;
+  const float denom = sqrtf(vi) / bc2sqrt + eps;
+  pi -= (lr / bc1) * (mi / denom);
+  p = pi; m = mi; v = vi;
+}
+
+__global__ __launch_bounds__(256) void adamw_clip_kernel(float* p, const float* g, float* m, float* v, int64_t n4, const float* state,
+                                                         const float* clip, float b1, float b2, float eps, float wd) {
+  if (clip[3] == 0.f) return;                      // non-finite gradient norm: the step is skipped, nothing is written
+  const float lr = state[0], bc1 = state[2], bc2sqrt = state[3], gs = clip[1];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    float4 pv = kd_ld4(p + i * 4), mv = kd_ld4(m + i * 4), vv = kd_ld4(v + i * 4);
+    const float4 gv = kd_ld4(g + i * 4);
+    adamw_clip_elem(pv.x, gv.x, mv.x, vv.x, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    adamw_clip_elem(pv.y, gv.y, mv.y, vv.y, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    adamw_clip_elem(pv.z, gv.z, mv.z, vv.z, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    adamw_clip_elem(pv.w, gv.w, mv.w, vv.w, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    kd_st4(p + i * 4, pv); kd_st4(m + i * 4, mv); kd_st4(v + i * 4, vv);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t kd_grad_sumsq_ws_bytes(int64_t n) { return (size_t)gsq_blocks(n) * sizeof(double); }
+
+// ws[b] (double) = the sum of g[i]^2 over the float4s block b owns, b < kd_grad_sumsq_ws_bytes(n) / 8
+int kd_grad_sumsq_partials(const float* g, int64_t n, void* ws, size_t ws_bytes, void* stream) {
+  KD_REQUIRE(g && ws && n > 0 && n % 4 == 0, KD_ERR_ARG, "kd_grad_sumsq_partials: bad args (n must be a positive multiple of 4)");
+  KD_REQUIRE(kd_aligned16(g) && (reinterpret_cast<uintptr_t>(ws) & 7u) == 0, KD_ERR_ALIGN,
+             "kd_grad_sumsq_partials: g must be 16-byte aligned, ws 8-byte aligned");
+  const int64_t grid = gsq_blocks(n);
+  KD_REQUIRE(ws_bytes >= (size_t)grid * sizeof(double), KD_ERR_WORKSPACE, "kd_grad_sumsq_partials: workspace too small");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, g, n / 4, (double*)ws);
+  return kd_check_launch("kd_grad_sumsq_partials");
+}
+
+// kd_adamw_step_dev with the gradients clipped to a global L2 norm of max_norm (see include/kd_hip.h).  Three launches: the
+// partial sums of squares, the one-block tick, the update.  A non-finite norm skips the step on the device.
+int kd_adamw_step_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, float* clip_state, void* ws,
+                           size_t ws_bytes, float beta1, float beta2, float eps, float weight_decay, float ginv, float max_norm,
+                           void* stream) {
+  KD_REQUIRE(p && g && m && v && state && clip_state && ws && n > 0 && n % 4 == 0, KD_ERR_ARG,
+             "kd_adamw_step_clip_dev: bad args (n must be a positive multiple of 4)");
+  KD_REQUIRE(std::isfinite(max_norm) && max_norm > 0.f, KD_ERR_ARG, "kd_adamw_step_clip_dev: max_norm must be finite and > 0 (got %g)",
+             (double)max_norm);
+  KD_REQUIRE(kd_aligned16(p) && kd_aligned16(g) && kd_aligned16(m) && kd_aligned16(v) && (reinterpret_cast<uintptr_t>(ws) & 7u) == 0,
+             KD_ERR_ALIGN, "kd_adamw_step_clip_dev: p, g, m, v must be 16-byte aligned, ws 8-byte aligned");
+  const int64_t nblk = gsq_blocks(n);
+  KD_REQUIRE(ws_bytes >= (size_t)nblk * sizeof(double), KD_ERR_WORKSPACE, "kd_adamw_step_clip_dev: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nblk), dim3(256), 0, st, g, n / 4, (double*)ws);
+  hipLaunchKernelGGL(adamw_clip_tick_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, (int)nblk, state, clip_state, beta1, beta2,
+                     ginv, max_norm);
+  int64_t grid = (n / 4 + 255) / 256;
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)grid), dim3(256), 0, st, p, g, m, v, n / 4, (const float*)state,
+                     (const float*)clip_state, beta1, beta2, eps, weight_decay);
+  return kd_check_launch("kd_adamw_step_clip_dev");
+}
+
+}  // extern "C"

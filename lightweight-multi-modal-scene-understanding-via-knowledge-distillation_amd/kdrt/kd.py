@@ -76,6 +76,8 @@ class KDStep:
         self.sink.end_step()
         self.opt.grad_scale = self.reducer.finish() if self.reducer is not None else 1.0
         self.opt.step()
+        if self.opt.max_grad_norm is not None:
+            parts["grad_norm"] = self.opt.last_grad_norm      # device scalar (pre-clip norm of the applied gradient): no sync
         parts["total"] = total
         parts["logits"] = zs.detach()
         return parts
@@ -134,6 +136,8 @@ class GraphedKDStep:
         s.sink.end_step()
         s.opt.grad_scale = s.reducer.finish() if s.reducer is not None else 1.0
         s.opt.enqueue_update()
+        if s.opt.max_grad_norm is not None:
+            parts["grad_norm"] = s.opt.last_grad_norm
         parts["total"] = total
         parts["logits"] = zs.detach()
         return parts

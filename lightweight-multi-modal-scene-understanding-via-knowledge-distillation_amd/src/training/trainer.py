@@ -80,7 +80,7 @@ class SegmentationMetrics:
 
 class Trainer:
     def __init__(self, model, train_loader, val_loader, device, lr=1e-3, weight_decay=1e-3, save_dir="checkpoints",
-                 class_weights=None, num_epochs=20):
+                 class_weights=None, num_epochs=20, max_grad_norm=None):
         self.model = model
         self.train_loader = train_loader
         self.val_loader = val_loader
@@ -91,7 +91,7 @@ class Trainer:
         self.class_weights = class_weights
         self.ignore_index = -1
         self.criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
-        self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
+        self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         self.scheduler = optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=num_epochs, eta_min=1e-5)
         # Data parallel (torch.distributed initialised, world > 1): every rank starts from rank 0's weights and the
         # gradients are summed over ranks in buckets as backward produces them (kdrt.ddp), for plain CE training as for KD.
@@ -111,6 +111,14 @@ class Trainer:
         self.best_miou = 0.0
         self.history_path = os.path.join(save_dir, "training_history.json")
         self.history = {"train_loss": [], "train_miou": [], "val_loss": [], "val_miou": [], "lr": []}
+        # global-norm gradient clipping (FusedAdamW(max_grad_norm=...)): off by default, and the history then keeps the
+        # reference's layout; on, it gains the epoch mean of the pre-clip gradient norm and the count of skipped steps.
+        # Under data parallelism the norm is taken after reducer.finish(), over the summed buffer, so every rank computes
+        # the same coefficient and the same skip decision without a further collective.
+        self.max_grad_norm = max_grad_norm
+        if max_grad_norm is not None:
+            self.history.update({"grad_norm": [], "skipped_steps": []})
+        self.last_epoch_grad_norm = None
 
     def _log(self, *a, **k):
         """Console output of the training loop: rank 0 only under data parallelism (errors and warnings of the other
@@ -146,6 +154,7 @@ class Trainer:
         self.model.train()
         metrics = SegmentationMetrics(num_classes=2, device=self.device)
         total = torch.zeros((), device=self.device)
+        gnorm = torch.zeros((), device=self.device) if self.max_grad_norm is not None else None
         if hasattr(self.train_loader, "set_epoch"):       # rank-sharded loaders reshuffle per epoch, identically on all ranks
             self.train_loader.set_epoch(self.epoch)
         for batch in tqdm(self.train_loader, desc="Train", disable=not self.is_main):
@@ -154,7 +163,11 @@ class Trainer:
             seg = batch["segmentation"].to(self.device, non_blocking=True)
             loss, logits = self._step(imgs, pts, seg)
             total += loss                      # stays on the device: no per-step sync
+            if gnorm is not None:
+                gnorm += self.optimizer.last_grad_norm
             metrics.update(logits, seg)
+        if gnorm is not None:                  # identical on every rank: no mean over ranks (a skipped step's inf / NaN shows here)
+            self.last_epoch_grad_norm = gnorm.item() / max(len(self.train_loader), 1)
         return self._mean_over_ranks(total, len(self.train_loader)), metrics.compute()
 
     def validate(self):
@@ -197,6 +210,9 @@ class Trainer:
         for k, v in zip(("train_loss", "train_miou", "val_loss", "val_miou", "lr"),
                         (train_loss, train_miou, val_loss, val_miou, lr)):
             self.history[k].append(v)
+        if self.max_grad_norm is not None:
+            self.history["grad_norm"].append(self.last_epoch_grad_norm)
+            self.history["skipped_steps"].append(self.optimizer.skipped_steps())
         if self.is_main:                       # one writer: ranks share the working directory
             with open(self.history_path, "w") as f:
                 json.dump(self.history, f, indent=2)

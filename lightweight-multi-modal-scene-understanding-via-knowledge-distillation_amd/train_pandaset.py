@@ -33,7 +33,8 @@ def main():
         print(f"  {k.capitalize()} params: {s[k + '_params']}")
     save_dir = "checkpoints/pandaset_weighted"
     trainer = Trainer(model=model, train_loader=train_loader, val_loader=val_loader, device=device, lr=1e-3,
-                      weight_decay=1e-3, save_dir=save_dir, class_weights=[0.39, 2.61, 33.09], num_epochs=30)
+                      weight_decay=1e-3, save_dir=save_dir, class_weights=[0.39, 2.61, 33.09], num_epochs=30,
+                      max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None)
     start_epoch = 0
     ckpt_path = os.path.join(save_dir, "latest.pth")
     if os.path.exists(ckpt_path):

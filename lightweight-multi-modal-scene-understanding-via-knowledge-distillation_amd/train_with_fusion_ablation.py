@@ -55,7 +55,8 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
     if base != 32:
         log(f"  Student camera encoder: base_channels={base}, {summary['camera_params']} params")
     kw = dict(lr=1e-3, weight_decay=1e-3, save_dir=f"checkpoints/fusion_ablation_{fusion_type}",
-              class_weights=[0.4, 3.5], num_epochs=int(os.environ.get("KD_EPOCHS", 20)))
+              class_weights=[0.4, 3.5], num_epochs=int(os.environ.get("KD_EPOCHS", 20)),
+              max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None)
     if teacher_ckpt:
         teacher = build_model("concat", 256, device)
         teacher.load_state_dict(torch.load(teacher_ckpt, map_location=device)["model_state"])
