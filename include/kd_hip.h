@@ -392,6 +392,19 @@ size_t kd_seg_loss_ws_bytes(int64_t npix);
 int kd_seg_loss_fwd_bwd(const float* zs, const float* zt, const int64_t* target, const float* class_w,
                         int ignore_index, float T, float alpha, float gscale, const float* gscale_dev, float* losses,
                         float* dzs, int B, int NC, int HW, void* ws, size_t ws_bytes, void* stream);
+/* The opt-in region-based hard-label loss: vals[0] = wf * Focal + wt * Tversky in place of the weighted CE,
+ *   Focal   = sum_K w[y] (1 - p_y)^gamma (-log p_y) / sum_K w[y],   K = the pixels kd_seg_loss_fwd_bwd keeps, p = softmax(zs),
+ *   Tversky = 1 - (1/NC) sum_c (TP_c + s) / (TP_c + a FP_c + b FN_c + s) over the kept pixels of the whole call (no class weights).
+ * Arguments as kd_seg_loss_fwd_bwd (zt NULL: no KL; dzs NULL: forward only; dzs = gscale * gscale_dev[0] * d/dzs (vals[0] +
+ * alpha*T^2*KL)) plus gamma (0 or >= 1), wf, wt (>= 0, not both 0), a, b (>= 0), s (> 0); anything else is KD_ERR_ARG.  vals holds
+ * 17 floats: [0] L_hard [1] KL [2] sum of weights [3] Focal [4] Tversky [5..8] TI_c [9..16] the per-class gradient coefficients the
+ * gradient pass reads.  A term whose weight is 0 is not evaluated (reported as 0); no kept pixel and wf > 0: vals[0] is NaN like the
+ * CE.  Three launches, no atomics, no host reads, ws = kd_seg_region_loss_ws_bytes(B * HW) bytes: bit-identical from call to call. */
+size_t kd_seg_region_loss_ws_bytes(int64_t npix);
+int kd_seg_region_loss_fwd_bwd(const float* zs, const float* zt, const int64_t* target, const float* class_w, int ignore_index,
+                               float T, float alpha, float gscale, const float* gscale_dev, float gamma, float wf, float wt,
+                               float a, float b, float s, float* vals, float* dzs, int B, int NC, int HW, void* ws,
+                               size_t ws_bytes, void* stream);
 size_t kd_mse_ws_bytes(int64_t n);
 int kd_mse_fwd_bwd(const float* a, const float* b, int64_t n, float gcoef, const float* gscale_dev, float* loss,
                    float* da, void* ws, size_t ws_bytes, void* stream);

@@ -24,7 +24,7 @@ class KDStep:
     def __init__(self, student, teacher, optimizer: FusedAdamW, class_weights: Optional[torch.Tensor] = None,
                  T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
                  reducer: Optional[BucketedAllReduce] = None, teacher_storage: str = "fp32",
-                 fused_objective: bool = True):
+                 fused_objective: bool = True, hard_loss=None):
         if teacher_storage not in ("fp32", "bf16"):
             raise ValueError(f"teacher_storage must be 'fp32' or 'bf16', got {teacher_storage!r}")
         # fused objective (default): loss values and loss gradients from the same kernel passes, feature-MSE gradients added
@@ -36,6 +36,9 @@ class KDStep:
         self.teacher_storage = teacher_storage
         self.student, self.teacher, self.opt = student, teacher, optimizer
         self.cw, self.T, self.alpha, self.beta, self.ignore_index = class_weights, T, alpha, beta, ignore_index
+        # hard_loss (kdrt.losses.RegionLoss): wf*Focal + wt*Tversky as the hard-label term instead of the weighted CE; None keeps
+        # the CE.  Data parallel: the Tversky sums cover each rank's own shard, the reducer averages the per-rank gradients.
+        self.hard_loss = hard_loss
         self.reducer = reducer
         self.sink = gradsink.install(optimizer.flat, reducer)      # backward kernels write into the flat grad buffer
         self.teacher.eval()
@@ -53,8 +56,8 @@ class KDStep:
         """Loss values + the student's backward pass -> (total, parts of detached device scalars)."""
         a = (zs, ms, zt, mt, labels, self.cw, self.T, self.alpha, self.beta, self.ignore_index)
         if self.fused_objective:
-            return kd_objective_backward(*a)
-        total, parts = kd_objective(*a)
+            return kd_objective_backward(*a, hard_loss=self.hard_loss)
+        total, parts = kd_objective(*a, hard_loss=self.hard_loss)
         gradsink.drop_pending()
         total.backward()
         if gradsink.pending():

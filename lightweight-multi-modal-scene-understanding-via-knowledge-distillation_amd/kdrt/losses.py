@@ -2,6 +2,8 @@
 
   seg_loss      : weighted CE with ignore_index (trainer.py:55,88), optionally + alpha*T^2*KL to a
                   teacher's logits -- value and dL/dlogits produced by one fused HIP call
+  region_seg_loss : the opt-in hard-label loss wf*Focal + wt*Tversky (RegionLoss) in place of the weighted CE, same fused
+                  form (csrc/kd_loss_region.hip; definition in DESIGN.md section 3)
   feature_mse   : F.mse_loss forward + gradient
   kd_objective  : CE + alpha*T^2*KL + beta*(MSE(cam) + MSE(lidar))   (the
                   reference has no KD code -- this definition is the build's specification)
@@ -12,6 +14,8 @@
 """
 from __future__ import annotations
 
+import math
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import torch
@@ -93,6 +97,100 @@ def seg_loss(logits, target, class_weights: Optional[torch.Tensor] = None, ignor
     return _SegLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T, alpha)
 
 
+@dataclass(frozen=True)
+class RegionLoss:
+    """Parameters of the region-based hard-label loss  L_hard = wf * Focal + wt * Tversky  (DESIGN.md section 3):
+
+      Focal   = sum_K w[y] (1 - p_y)^gamma (-log p_y) / sum_K w[y]      K: the pixels the weighted CE keeps, p = softmax(logits)
+      Tversky = 1 - (1/NC) sum_c (TP_c + s) / (TP_c + a*FP_c + b*FN_c + s)   soft counts over K, all NC classes, no class weights
+
+    gamma = 0 makes Focal the weighted CE; a = b = 0.5 makes Tversky the Dice loss.  A term whose weight is 0 is not evaluated.
+    With wf > 0 a batch without a kept pixel gives NaN, as the CE does (0/0); with wf == 0 it gives the Tversky value and a zero
+    gradient.  The Tversky sums run over the batch of ONE call: under data parallelism each rank forms them over its own shard
+    (like the BatchNorm statistics) and the reducer averages the per-rank gradients, so the optimised loss is the mean of the
+    per-rank losses, which is not the Tversky loss of the global batch."""
+    gamma: float = 2.0
+    wf: float = 1.0
+    wt: float = 1.0
+    a: float = 0.7
+    b: float = 0.3
+    s: float = 1.0
+
+    def __post_init__(self):
+        for k in ("gamma", "wf", "wt", "a", "b", "s"):
+            v = getattr(self, k)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"RegionLoss: {k} must be a finite number, got {v!r}")
+        if not (self.gamma == 0 or self.gamma >= 1):
+            raise ValueError(f"RegionLoss: gamma must be 0 or >= 1 (the focal derivative is unbounded at p_y -> 1 in between), got {self.gamma}")
+        if self.a < 0 or self.b < 0 or self.s <= 0:
+            raise ValueError(f"RegionLoss: need a >= 0, b >= 0 and s > 0, got a={self.a} b={self.b} s={self.s}")
+        if self.wf < 0 or self.wt < 0 or (self.wf == 0 and self.wt == 0):
+            raise ValueError(f"RegionLoss: need wf >= 0 and wt >= 0, not both 0, got wf={self.wf} wt={self.wt}")
+
+    def args(self):
+        return tuple(float(getattr(self, k)) for k in ("gamma", "wf", "wt", "a", "b", "s"))
+
+
+REGION_VALS = 17          # floats kd_seg_region_loss_fwd_bwd writes: L_hard, KL, sum w, Focal, Tversky, TI_c[4], gradient coefficients[8]
+
+
+def _check_region_spec(spec):
+    if not isinstance(spec, RegionLoss):
+        raise KDError(f"the hard-label loss must be a kdrt.losses.RegionLoss (or None for the weighted CE), got {type(spec).__name__}")
+
+
+def _region_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, vals, dzs):
+    B, NC, H, W = zs.shape
+    nbytes = lib.kd_seg_region_loss_ws_bytes(B * H * W)
+    ws = ops.workspace(nbytes, zs.device)
+    lib.call("kd_seg_region_loss_fwd_bwd", P(zs), P(zt), P(target), P(class_w), int(ignore_index), float(T), float(alpha),
+             1.0, P(gdev), *spec.args(), P(vals), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
+
+
+class _RegionLossFn(torch.autograd.Function):
+    """_SegLossFn with the region loss as the hard-label term: forward values only, backward one more fused call."""
+
+    @staticmethod
+    def forward(ctx, zs, zt, target, class_w, ignore_index, T, alpha, spec):
+        ops.require_gpu_tensor(zs, "region_seg_loss")
+        _check_region_spec(spec)
+        zs_c = zs.detach().contiguous()
+        zt_c = None if zt is None else zt.detach().contiguous()
+        target = target.contiguous()
+        if target.dtype != torch.int64:
+            raise KDError("segmentation target must be int64")
+        _check_target(zs_c, target)
+        _check_class_weights(zs_c, class_w)
+        vals = torch.empty(REGION_VALS, device=zs.device, dtype=torch.float32)
+        _region_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, vals, None)
+        ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec)
+        kl, focal, tversky, class_ti = vals[1], vals[3], vals[4], vals[5:5 + zs_c.shape[1]]
+        ctx.mark_non_differentiable(kl, focal, tversky, class_ti)
+        return vals[0], kl, focal, tversky, class_ti
+
+    @staticmethod
+    def backward(ctx, g_hard, *_):
+        # the gradient through `hard` is d(L_hard + alpha*T^2*KL)/dzs (kd_objective adds KL's value separately)
+        zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec = ctx.args
+        vals = torch.empty(REGION_VALS, device=zs_c.device, dtype=torch.float32)
+        dzs = torch.empty_like(zs_c)
+        _region_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, g_hard.contiguous().view(1), vals, dzs)
+        return dzs, None, None, None, None, None, None, None
+
+
+def region_seg_loss(logits, target, spec: RegionLoss, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
+                    teacher_logits: Optional[torch.Tensor] = None, T: float = 4.0, alpha: float = 1.0):
+    """-> (hard, kl, parts): seg_loss with hard = spec.wf * Focal + spec.wt * Tversky in place of the weighted CE (see RegionLoss;
+    class weights enter the focal term only).  The gradient that flows back through `hard` is that of hard + alpha*T^2*kl.
+    parts = {"focal", "tversky", "class_ti"}: device scalars and the [NC] vector of per-class Tversky indices (detached; a term
+    whose weight is 0 reads 0)."""
+    if teacher_logits is None:
+        alpha = 0.0
+    hard, kl, focal, tversky, class_ti = _RegionLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T, alpha, spec)
+    return hard, kl, {"focal": focal, "tversky": tversky, "class_ti": class_ti}
+
+
 class _MSEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -124,19 +222,29 @@ def feature_mse(student_feat, teacher_feat):
 
 
 def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
-                 class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1):
-    """total = CE + alpha*T^2*KL + beta*(MSE(camera_feat) + MSE(lidar_feat)); returns (total, parts)."""
-    ce, kl = seg_loss(student_logits, target, class_weights, ignore_index, teacher_logits, T, alpha)
+                 class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
+                 hard_loss: Optional[RegionLoss] = None):
+    """total = CE + alpha*T^2*KL + beta*(MSE(camera_feat) + MSE(lidar_feat)); returns (total, parts).
+    hard_loss (a RegionLoss): wf*Focal + wt*Tversky takes the CE's place; parts["ce"] then carries it and parts gains "focal"
+    and "tversky".  Under data parallelism the Tversky sums cover this rank's shard (see RegionLoss)."""
+    extra = {}
+    if hard_loss is None:
+        ce, kl = seg_loss(student_logits, target, class_weights, ignore_index, teacher_logits, T, alpha)
+    else:
+        ce, kl, rp = region_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
+        extra = {"focal": rp["focal"], "tversky": rp["tversky"]}
     mse_c = feature_mse(student_mids["camera_feat"], teacher_mids["camera_feat"])
     mse_l = feature_mse(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
     # `ce` carries the CE+KL gradient; add KL's value without a second gradient path
     total = ce + (alpha * T * T) * kl.detach() + beta * (mse_c + mse_l)
-    return total, {"ce": ce.detach(), "kl": kl.detach(), "mse_cam": mse_c.detach(), "mse_lidar": mse_l.detach()}
+    return total, {"ce": ce.detach(), "kl": kl.detach(), "mse_cam": mse_c.detach(), "mse_lidar": mse_l.detach(), **extra}
 
 
 def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
-                          class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1):
+                          class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
+                          hard_loss: Optional[RegionLoss] = None):
     """kd_objective(...)[0].backward() in one: returns (total, parts) with the student's gradients already propagated.
+    hard_loss as in kd_objective: the region-loss call writes dL/dlogits together with L_hard / KL in the CE call's place.
 
     Same values and the same gradient bits as the autograd formulation, fewer passes: the segmentation-loss call writes
     dL/dlogits together with CE / KL; each feature MSE writes its gradient in the pass that sums its value, and that
@@ -159,8 +267,16 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     dzs = torch.empty_like(zs_c)
     nbytes = lib.kd_seg_loss_ws_bytes(B * H * W)
     ws = ops.workspace(nbytes, dev)
-    lib.call("kd_seg_loss_fwd_bwd", P(zs_c), P(zt_c), P(target), P(class_weights), int(ignore_index), float(T), float(alpha),
-             1.0, None, P(vals), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
+    hard = vals                                                   # [0] the hard-label term, [1] KL: what the final kernel reads
+    extra = {}
+    if hard_loss is None:
+        lib.call("kd_seg_loss_fwd_bwd", P(zs_c), P(zt_c), P(target), P(class_weights), int(ignore_index), float(T), float(alpha),
+                 1.0, None, P(vals), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
+    else:
+        _check_region_spec(hard_loss)
+        hard = torch.empty(REGION_VALS, device=dev, dtype=torch.float32)
+        _region_call(hard_loss, zs_c, zt_c, target, class_weights, ignore_index, T, alpha, None, hard, dzs)
+        extra = {"focal": hard[3], "tversky": hard[4]}
     roots, grads = [zs], [dzs]
     gradsink.drop_pending()
     slabs, counts = [], []
@@ -179,14 +295,14 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
         if want:
             gradsink.deposit(am, da)
     # the two MSE values and the total in one launch (vals[4], vals[5], vals[6])
-    lib.call("kd_kd_objective_final", P(vals), P(slabs[0]), counts[0], P(slabs[1]), counts[1], float(alpha * T * T), float(beta), P(vals[4:]),
+    lib.call("kd_kd_objective_final", P(hard), P(slabs[0]), counts[0], P(slabs[1]), counts[1], float(alpha * T * T), float(beta), P(vals[4:]),
              stream())
     torch.autograd.backward(roots, grads)
     if gradsink.pending():
         gradsink.drop_pending()
         raise KDError("kd_objective_backward: a feature-map gradient was not collected by the fusion block's backward "
                       "(unsupported model structure for the fused objective; use kd_objective(...).backward())")
-    return vals[6], {"ce": vals[0], "kl": vals[1], "mse_cam": vals[4], "mse_lidar": vals[5]}
+    return vals[6], {"ce": hard[0], "kl": hard[1], "mse_cam": vals[4], "mse_lidar": vals[5], **extra}
 
 
 def confusion(logits, target, num_classes: int = 2, ignore_index: int = -1, out: Optional[torch.Tensor] = None):

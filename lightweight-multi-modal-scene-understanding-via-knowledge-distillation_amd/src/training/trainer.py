@@ -22,7 +22,7 @@ import torch.optim as optim
 from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
-from kdrt.losses import confusion, seg_loss
+from kdrt.losses import RegionLoss, confusion, region_seg_loss, seg_loss
 from kdrt.optim import FusedAdamW
 
 try:
@@ -80,7 +80,7 @@ class SegmentationMetrics:
 
 class Trainer:
     def __init__(self, model, train_loader, val_loader, device, lr=1e-3, weight_decay=1e-3, save_dir="checkpoints",
-                 class_weights=None, num_epochs=20, max_grad_norm=None):
+                 class_weights=None, num_epochs=20, max_grad_norm=None, hard_loss=None):
         self.model = model
         self.train_loader = train_loader
         self.val_loader = val_loader
@@ -90,7 +90,15 @@ class Trainer:
             class_weights = torch.FloatTensor(class_weights).to(device)
         self.class_weights = class_weights
         self.ignore_index = -1
-        self.criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
+        # hard_loss (kdrt.losses.RegionLoss): train AND validate with wf*Focal + wt*Tversky instead of the weighted CE (the class
+        # weights then enter the focal term only).  Data parallel: the Tversky sums cover each rank's own shard of the batch.
+        if hard_loss is not None and not isinstance(hard_loss, RegionLoss):
+            raise ValueError(f"hard_loss must be a kdrt.losses.RegionLoss or None, got {type(hard_loss).__name__}")
+        self.hard_loss = hard_loss
+        if hard_loss is None:
+            self.criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
+        else:
+            self.criterion = lambda logits, seg: region_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
         self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         self.scheduler = optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=num_epochs, eta_min=1e-5)
         # Data parallel (torch.distributed initialised, world > 1): every rank starts from rank 0's weights and the
@@ -250,7 +258,7 @@ class Trainer:
 
 class KDTrainer(Trainer):
     """Teacher -> student distillation on top of `Trainer`.  total = CE + alpha*T^2*KL + beta*(MSE(camera_feat)
-    + MSE(lidar_feat)); the teacher runs in eval mode under no_grad.  With torch.distributed initialised the
+    + MSE(lidar_feat)) (`hard_loss=RegionLoss(...)`: focal + Tversky in the CE's place); the teacher runs in eval mode under no_grad.  With torch.distributed initialised the
     student is broadcast from rank 0 and gradients are all-reduced in buckets overlapped with backward."""
 
     def __init__(self, model, teacher, train_loader, val_loader, device, T=4.0, alpha=1.0, beta=1.0, **kw):
@@ -258,7 +266,8 @@ class KDTrainer(Trainer):
         self.teacher = teacher
         if distributed():
             broadcast_module(teacher)           # (a teacher loaded from the same checkpoint on every rank: a no-op in value)
-        self.kd_step = KDStep(model, teacher, self.optimizer, self.class_weights, T, alpha, beta, self.ignore_index, self.reducer)
+        self.kd_step = KDStep(model, teacher, self.optimizer, self.class_weights, T, alpha, beta, self.ignore_index, self.reducer,
+                              hard_loss=self.hard_loss)
         self.sink = self.kd_step.sink
 
     def _step(self, imgs, pts, seg):

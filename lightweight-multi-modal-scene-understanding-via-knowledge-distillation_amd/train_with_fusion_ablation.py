@@ -7,6 +7,9 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
   KD_STUDENT_BASE_CHANNELS   with KD_TEACHER: the student's TwinLiteEncoder width, one of 8 16 24 32 40 (default 32, the
                  teacher's); the teacher is always built at 32 to load its checkpoint
   KD_EPOCHS / KD_BATCH_SIZE   20 / 4
+  KD_HARD_LOSS   unset: the reference's weighted cross-entropy.  `focal_tversky`: focal + Tversky as the hard-label term
+                 (kdrt.losses.RegionLoss), for CE and KD training alike; KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA
+                 override its gamma (2), false-positive weight (0.7) and false-negative weight (0.3)
 Launch with `python -m torch.distributed.run --nproc-per-node N` for data-parallel training: one process per GPU,
 frames sharded over ranks in equal counts (every rank runs the same number of steps), rank 0's initial weights
 broadcast, gradients all-reduced in buckets during backward (CE and KD training alike), BatchNorm statistics per
@@ -42,6 +45,18 @@ def build_model(fusion_type, fusion_out_channels, device, num_classes=2, base_ch
                                      output_mode="same").to(device)
 
 
+def hard_loss_from_env(env=os.environ):
+    """KD_HARD_LOSS -> None (weighted CE) or the RegionLoss the KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA knobs describe"""
+    name = env.get("KD_HARD_LOSS", "")
+    if name in ("", "ce"):
+        return None
+    if name != "focal_tversky":
+        raise ValueError(f"KD_HARD_LOSS must be unset, 'ce' or 'focal_tversky', got {name!r}")
+    from kdrt.losses import RegionLoss
+    return RegionLoss(gamma=float(env.get("KD_FOCAL_GAMMA", 2.0)), a=float(env.get("KD_TVERSKY_ALPHA", 0.7)),
+                      b=float(env.get("KD_TVERSKY_BETA", 0.3)))
+
+
 def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, val_scenes, device):
     log(f"\n{'='*80}\nTRAINING: {fusion_type.upper()} FUSION\n{'='*80}")
     train_loader, val_loader = create_pandaset_dataloaders(
@@ -57,6 +72,9 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
     kw = dict(lr=1e-3, weight_decay=1e-3, save_dir=f"checkpoints/fusion_ablation_{fusion_type}",
               class_weights=[0.4, 3.5], num_epochs=int(os.environ.get("KD_EPOCHS", 20)),
               max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None)
+    kw["hard_loss"] = hard_loss_from_env()
+    if kw["hard_loss"] is not None:
+        log(f"  Hard-label loss: {kw['hard_loss']}")
     if teacher_ckpt:
         teacher = build_model("concat", 256, device)
         teacher.load_state_dict(torch.load(teacher_ckpt, map_location=device)["model_state"])
