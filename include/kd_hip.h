@@ -387,6 +387,42 @@ int kd_image_resize_bilinear_batch(const uint8_t* in, const int32_t* hbounds, co
                                    const int32_t* vk, int vks, float* out_f32chw, uint8_t* out_u8hwc, int B, int Hs, int Ws,
                                    int H, int W, void* stream);
 
+/* ---- opt-in training augmentation of a batch, in place (csrc/kd_augment.hip; no reference counterpart) ----------
+ * params: device float32 [B,16], one row per frame, drawn on the host by kdrt/augment.py frame_params as a pure function
+ * of (settings, seed, frame key).  Row layout (word: field):
+ *    0 c   1 s   2 scale   3 tx   4 ty   5 sx   6 sy   7 gi   8 a_r   9 a_g   10 a_b   11 b   12 mirror   13..15 padding
+ * (c, s: cosine and sine of the yaw; sx, sy: +1 / -1 flip signs; gi: intensity gain; a_*, b: image gains and offset;
+ * mirror: 0 or 1).  The draw: w0..w11 = the output words of Philox-4x32-10 at counters (0, 1, key lo, key hi),
+ * (1, 1, ..), (2, 1, ..) under the key (seed lo, seed hi), u_k = (w_k >> 8) * 2^-24, d(r, u) = r * (2u - 1) in double:
+ *    w0  yaw = d(rot_deg, u0) degrees; c, s = its cosine and sine (reduced to a multiple of 90 degrees plus a rest in
+ *        [-45, 45] first, so that 0, +-90 and +-180 degrees give exact 0 and +-1)
+ *    w1  scale = 1 + d(scale, u1)          w2  tx = d(translate, u2)          w3  ty = d(translate, u3)
+ *    w4  flipped = u4 < flip: the sign of flip_axis is -1 and mirror = 1
+ *    w5  gi = 1 + d(intensity, u5)         w6  brightness = d(brightness, u6)  w7  contrast = 1 + d(contrast, u7)
+ *    w8, w9, w10  channel gain r, g, b = 1 + d(channel_gain, u)
+ *    w11 dropped = u11 < camera_drop: a_r = a_g = a_b = b = 0
+ *    a_c = gain_c * contrast,  b = 0.5 * (1 - contrast) + brightness;  every field computed in double, rounded once.
+ * Counter word 1 keeps the streams apart: 0 is the subset sampler of kd_points_prepare_batch, 1 these parameters, 2 the
+ * per-point jitter.  tests/_augment_ref.py is the numpy mirror of both kernels and of the draw.
+ *
+ * kd_points_augment_batch: x, y, z, intensity are the packed columns of B ragged frames (offsets, frame_keys as in
+ * kd_points_prepare_batch), rewritten in place.  Point j of frame b, every operation a separately rounded float32 one:
+ *    xf = sx*x;  yf = sy*y;  xr = c*xf - s*yf;  yr = s*xf + c*yf;
+ *    x' = (scale*xr + tx) + jx;  y' = (scale*yr + ty) + jy;  z' = scale*z + jz;  i' = gi*i
+ * with j? = jitter * ((word? >> 8) * 2^-23 - 1) from words 0, 1, 2 of Philox-4x32-10(counter = (j, 2, frame_keys[b] low
+ * word, high word), key = (seed low word, high word)).  jitter == 0: no jitter term is added and no Philox block is
+ * computed.  NaN rows stay NaN.  Run it before kd_bev_rasterize and kd_points_prepare_batch: labels and points then see
+ * the same coordinates.  A frame's result depends on its own points, row, key, seed and jitter only.  16-byte accesses
+ * where the four columns of a frame sit alike within a 16-byte line (a column stride that is a multiple of 4 floats
+ * gives that), 4-byte accesses otherwise.  No workspace, no atomics.
+ *
+ * kd_image_augment_batch: img[B,3,H,W] float32 in place, v' = min(max(v*a_c + b, 0), 1) (product and sum rounded
+ * separately); with mirror != 0 the columns w and W-1-w of every row swap.  Any W >= 1; 16-byte accesses when W is a
+ * multiple of 8 and img is 16-byte aligned. */
+int kd_points_augment_batch(float* x, float* y, float* z, float* intensity, const int64_t* offsets, const uint64_t* frame_keys,
+                            const float* params, int B, int64_t n_total, uint64_t seed, float jitter, void* stream);
+int kd_image_augment_batch(float* img, const float* params, int B, int H, int W, void* stream);
+
 /* ---- losses, metric, optimiser (trainer.py:18-37,55-56,86-90; KD terms are build-defined) ------ */
 size_t kd_seg_loss_ws_bytes(int64_t npix);
 int kd_seg_loss_fwd_bwd(const float* zs, const float* zt, const int64_t* target, const float* class_w,

@@ -128,6 +128,19 @@ __device__ __forceinline__ float kd_wave_sum(float v) {
   return v;
 }
 
+// Philox-4x32-10 (Salmon et al., SC'11; Random123's philox4x32_R(10, ...)), the whole output block.  Word 0 is what
+// kd_input.hip's philox_word0 returns for the same counter and key.
+__device__ __forceinline__ uint4 kd_philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return make_uint4(c0, c1, c2, c3);
+}
+
 // out[i] = sum_s slab[s][i], s in fixed order (deterministic); defined in kd_runtime.hip
 int kd_nt_store(size_t bytes);       // 1: a tensor of this size (>= 64 MiB) should be stored with the non-temporal hint
 int kd_slab_reduce_launch(const float* slab, int nsplit, int64_t n, float* out, hipStream_t st);

@@ -17,6 +17,12 @@ keyed on (`sample_seed`, epoch, dataset index).
 full-size uint8 frames travel to the GPU and kd_image_resize_bilinear_batch produces the float32 [B,3,H,W] batch with
 Pillow's exact bytes (integer resample over host-built coefficient tables, kdrt/resample.py).
 
+`augment=Augment(...)` (opt-in, default off, training loader only; kdrt/augment.py) transforms each batch on the device
+before anything reads it: kd_points_augment_batch rewrites the packed point columns (joint flip, yaw, scale, translation,
+jitter, intensity gain) ahead of the rasteriser and the point stacker, so BEV labels and points agree by construction,
+and kd_image_augment_batch adjusts the float32 image batch (gains, offset, clamp, the flip's mirror, camera dropout).
+Every frame's transform is a function of (`sample_seed`, epoch, dataset index) alone.
+
 `SyntheticPandaSet` serves frames of the same contract when there is no dataset on disk:
     image        float32 [3, 256, 256] in [0, 1]
     points       float32 [max_points, 4]  (x, y, z, intensity), zero-padded tail
@@ -32,6 +38,7 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 from kdrt import KDError
+from kdrt.augment import Augment, as_augment, frame_params
 from kdrt.lib import lib
 from kdrt.ops import P, stream, workspace
 from kdrt.resample import device_tables
@@ -145,12 +152,30 @@ def resize_images_pil_bilinear(img_u8_bhwc, size: Tuple[int, int], want_u8: bool
     return (out, u8) if want_u8 else out
 
 
+def _u64(v: int) -> int:
+    return int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+def _augment_launches(aug: Augment, params, x, y, z, w, off, keys, B: int, n: int, sample_seed: int, s: int):
+    """kd_points_augment_batch over the packed columns of a batch, in place, on stream `s` (skipped when no point
+    setting is on: the columns then keep their bits)."""
+    if aug.points_on and n > 0:
+        lib.call("kd_points_augment_batch", P(x), P(y), P(z), P(w), P(off), P(keys), P(params), B, n, _u64(sample_seed),
+                 _f32(aug.jitter), s)
+
+
+def _augment_image_launch(aug: Augment, params, img: torch.Tensor, s: int):
+    """kd_image_augment_batch over float32 [B,3,H,W], in place, on stream `s` (skipped when no image setting is on)."""
+    if aug.image_on:
+        lib.call("kd_image_augment_batch", P(img), P(params), int(img.shape[0]), int(img.shape[2]), int(img.shape[3]), s)
+
+
 class StagingSet:
     """Pinned host buffers of ONE batch in flight (grow-only) + the event after its host-to-device copies: the buffers
     are not refilled before that event has completed."""
 
     def __init__(self):
-        self.cols = self.cls = self.img = self.meta = None
+        self.cols = self.cls = self.img = self.meta = self.aug = None
         self.copied = None
 
     def _fit(self, name: str, numel: int, dtype) -> np.ndarray:
@@ -160,9 +185,10 @@ class StagingSet:
             setattr(self, name, buf)
         return buf.numpy()
 
-    def fill(self, raws: Sequence[Dict[str, object]], frame_keys: Sequence[int]):
-        """-> (lens, image shape) after packing the batch: cols = x | y | z | i (each n_total float32), cls (n_total
-        int64), img [B,H,W,3] uint8, meta = offsets [B+1] | frame keys [B] (int64)."""
+    def fill(self, raws: Sequence[Dict[str, object]], frame_keys: Sequence[int], col_align: int = 1, params: np.ndarray = None):
+        """-> (lens, image shape) after packing the batch: cols = x | y | z | i (each n_total float32, column c at
+        c * stride, stride = n_total rounded up to `col_align`: kept in `self.stride`), cls (n_total int64), img [B,H,W,3]
+        uint8, meta = offsets [B+1] | frame keys [B] (int64), and -- with `params` -- aug = the float32 [B,16] rows."""
         if self.copied is not None:
             self.copied.synchronize()
         B = len(raws)
@@ -170,9 +196,10 @@ class StagingSet:
         n = sum(lens)
         if any(int(np.shape(r[k])[0]) != m for r, m in zip(raws, lens) for k in ("y", "z", "i", "class")):
             raise KDError("x, y, z, i and class must have the same length per frame")
-        cols = self._fit("cols", 4 * n, torch.float32)
+        ns = self.stride = -(-n // col_align) * col_align
+        cols = self._fit("cols", 4 * ns, torch.float32)
         for c, k in enumerate("xyzi"):
-            np.concatenate([np.asarray(r[k], np.float32).reshape(-1) for r in raws], out=cols[c * n:(c + 1) * n])
+            np.concatenate([np.asarray(r[k], np.float32).reshape(-1) for r in raws], out=cols[c * ns:c * ns + n])
         np.concatenate([np.asarray(r["class"], np.int64).reshape(-1) for r in raws], out=self._fit("cls", n, torch.int64)[:n])
         shape = tuple(np.shape(raws[0]["image_u8"]))
         if len(shape) != 3 or shape[2] != 3 or any(tuple(np.shape(r["image_u8"])) != shape for r in raws):
@@ -184,6 +211,8 @@ class StagingSet:
         meta[0] = 0
         np.cumsum(lens, out=meta[1:B + 1])
         meta[B + 1:2 * B + 1] = np.asarray([k & 0xFFFFFFFFFFFFFFFF for k in frame_keys], np.uint64).view(np.int64)
+        if params is not None:
+            self._fit("aug", params.size, torch.float32)[:params.size] = params.reshape(-1)
         return lens, shape
 
 
@@ -248,8 +277,12 @@ class PandaSetDataset(Dataset):
             return resize_images_pil_bilinear(img_u8[None], self.image_size)[0]
         return image_to_chw(img_u8)
 
-    def prepare_batch(self, raws: Sequence[Dict[str, object]]) -> Dict[str, object]:
-        """Device stage for a list of `load_raw` results -> the collated batch the trainers consume."""
+    def prepare_batch(self, raws: Sequence[Dict[str, object]], augment: Augment = None, frame_keys: Sequence[int] = None,
+                      sample_seed: int = 0) -> Dict[str, object]:
+        """Device stage for a list of `load_raw` results -> the collated batch the trainers consume.  With `augment`
+        (and the frames' keys) the batch is transformed as in `prepare_batch_staged`, on the current stream."""
+        if augment is not None:
+            return self._prepare_batch_augmented(raws, augment, frame_keys, sample_seed)
         xs = [_dev(r["x"], torch.float32) for r in raws]
         ys = [_dev(r["y"], torch.float32) for r in raws]
         seg = rasterize_bev_batch(xs, ys, [r["class"] for r in raws], self.grid_size, self.pc_range, remap=True)
@@ -257,37 +290,85 @@ class PandaSetDataset(Dataset):
         img = torch.stack([self._image_chw(r["image_u8"]) for r in raws])
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
 
+    def _prepare_batch_augmented(self, raws, aug: Augment, frame_keys, sample_seed: int) -> Dict[str, object]:
+        """The synchronous path under augmentation: the frames' columns are concatenated on the device, transformed in
+        place by kd_points_augment_batch, then rasterised and stacked from there; the stacked images are adjusted by
+        kd_image_augment_batch.  Same kernels, rows and keys as the staged path: for sweeps of at most max_points points
+        the two paths give identical bits (longer sweeps are cut by torch.randperm here, by the device sampler there)."""
+        B = len(raws)
+        if B == 0 or frame_keys is None or len(frame_keys) != B:
+            raise KDError("an augmented batch needs at least one frame and one frame key per frame")
+        lens = [int(np.shape(r["x"])[0]) for r in raws]
+        if any(int(np.shape(r[k])[0]) != m for r, m in zip(raws, lens) for k in ("y", "z", "i", "class")):
+            raise KDError("x, y, z, i and class must have the same length per frame")
+        n = sum(lens)
+        ns = -(-n // 4) * 4                                    # column stride: 16-byte accesses in the kernel
+        cols = torch.empty(max(4 * ns, 1), dtype=torch.float32, device="cuda")
+        for c, k in enumerate("xyzi"):
+            if n:
+                torch.cat([_dev(r[k], torch.float32).reshape(-1) for r in raws], out=cols[c * ns:c * ns + n])
+        x, y, z, w = (cols[c * ns:c * ns + n] for c in range(4))
+        cls = torch.cat([_dev(r["class"], torch.int64).reshape(-1) for r in raws]) if n else torch.empty(1, dtype=torch.int64, device="cuda")
+        bounds = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        off = torch.from_numpy(bounds).cuda()
+        keys = torch.from_numpy(np.asarray([_u64(k) for k in frame_keys], np.uint64).view(np.int64)).cuda()
+        params = torch.from_numpy(frame_params(aug, sample_seed, frame_keys)).cuda()
+        s = stream()
+        _augment_launches(aug, params, x, y, z, w, off, keys, B, n, sample_seed, s)
+        GH, GW = int(self.grid_size[0]), int(self.grid_size[1])
+        x0, x1, y0, y1 = self.pc_range
+        seg = torch.empty(B, GH, GW, dtype=torch.int64, device="cuda")
+        nbytes = lib.kd_bev_rasterize_ws_bytes(B, GH, GW)
+        ws = workspace(nbytes, seg.device)
+        lib.call("kd_bev_rasterize", P(x), P(y), P(cls), P(off), B, n, 1, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
+                 _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws), nbytes, P(seg), s)
+        pts = torch.stack([prepare_points(*(v[a:b] for v in (x, y, z, w)), self.max_points)
+                           for a, b in zip(bounds[:-1].tolist(), bounds[1:].tolist())])
+        img = torch.stack([self._image_chw(r["image_u8"]) for r in raws])
+        _augment_image_launch(aug, params, img, s)
+        return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
+
     def prepare_batch_staged(self, raws: Sequence[Dict[str, object]], staging: StagingSet, side: "torch.cuda.Stream",
-                             frame_keys: Sequence[int], sample_seed: int = 0, ws_holder: list = None) -> Dict[str, object]:
+                             frame_keys: Sequence[int], sample_seed: int = 0, ws_holder: list = None,
+                             augment: Augment = None) -> Dict[str, object]:
         """`prepare_batch` for a whole batch at once, enqueued on the stream `side`: one host-to-device copy per tensor
         from the pinned `staging` set (packed point columns, class ids, uint8 images, offsets + frame keys), then three
         launches (rasteriser, batched points, batched images -- with `device_resize` and full-size frames the image
         launch is the Pillow-exact resize).  Sweeps longer than max_points are cut by the device
         sampler of kd_points_prepare_batch under (`sample_seed`, frame key).  The tensors returned belong to `side`:
         a consumer on another stream waits for an event recorded after this call and tells the allocator
-        (`record_stream`).  `ws_holder`: a one-element list that keeps the rasteriser's workspace of this stream."""
+        (`record_stream`).  `ws_holder`: a one-element list that keeps the rasteriser's workspace of this stream.
+        `augment`: one more copy (the frames' float32 [B,16] rows) and up to two more launches, kd_points_augment_batch
+        ahead of the rasteriser and kd_image_augment_batch after the image launch."""
         if not torch.cuda.is_available():
             raise KDError("input preparation runs on the MI355X; there is no CPU fallback")
         B = len(raws)
         if B == 0:
             raise KDError("prepare_batch_staged needs at least one frame")
-        lens, (H, W, _) = staging.fill(raws, frame_keys)
-        n = sum(lens)
+        if augment is None:
+            lens, (H, W, _) = staging.fill(raws, frame_keys)
+        else:                                                  # column stride a multiple of 4: 16-byte accesses in the kernel
+            lens, (H, W, _) = staging.fill(raws, frame_keys, col_align=4, params=frame_params(augment, sample_seed, frame_keys))
+        n, ns = sum(lens), staging.stride
         GH, GW = int(self.grid_size[0]), int(self.grid_size[1])
         x0, x1, y0, y1 = self.pc_range
         ws_holder = [None] if ws_holder is None else ws_holder
         with torch.cuda.stream(side):
-            cols = torch.empty(max(4 * n, 1), dtype=torch.float32, device="cuda")
+            cols = torch.empty(max(4 * ns, 1), dtype=torch.float32, device="cuda")
             cls = torch.empty(max(n, 1), dtype=torch.int64, device="cuda")
             img8 = torch.empty(B, H, W, 3, dtype=torch.uint8, device="cuda")
             meta = torch.empty(2 * B + 1, dtype=torch.int64, device="cuda")
-            cols[:4 * n].copy_(staging.cols[:4 * n], non_blocking=True)
+            cols[:4 * ns].copy_(staging.cols[:4 * ns], non_blocking=True)
             cls[:n].copy_(staging.cls[:n], non_blocking=True)
             img8.view(-1).copy_(staging.img[:img8.numel()], non_blocking=True)
             meta.copy_(staging.meta[:2 * B + 1], non_blocking=True)
+            params = None
+            if augment is not None:
+                params = torch.empty(B * 16, dtype=torch.float32, device="cuda")
+                params.copy_(staging.aug[:B * 16], non_blocking=True)
             staging.copied = torch.cuda.Event()
             staging.copied.record(side)
-            x, y, z, w = (cols[c * n:(c + 1) * n] for c in range(4))
+            x, y, z, w = (cols[c * ns:c * ns + n] for c in range(4))
             off, keys = meta[:B + 1], meta[B + 1:]
             seg = torch.empty(B, GH, GW, dtype=torch.int64, device="cuda")
             pts = torch.empty(B, self.max_points, 4, dtype=torch.float32, device="cuda")
@@ -298,6 +379,8 @@ class PandaSetDataset(Dataset):
             if ws_holder[0] is None or ws_holder[0].numel() < nbytes:      # this stream's own claim table: ops.workspace()
                 ws_holder[0] = torch.empty(nbytes, dtype=torch.uint8, device="cuda")   # is the compute stream's
             s = side.cuda_stream
+            if augment is not None:
+                _augment_launches(augment, params, x, y, z, w, off, keys, B, n, sample_seed, s)
             lib.call("kd_bev_rasterize", P(x), P(y), P(cls), P(off), B, n, 1, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
                      _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws_holder[0]), nbytes, P(seg), s)
             lib.call("kd_points_prepare_batch", P(x), P(y), P(z), P(w), P(off), P(keys), B, n, self.max_points,
@@ -306,6 +389,8 @@ class PandaSetDataset(Dataset):
                 _resize_launch(img8, (OW, OH), img, None, s)
             else:
                 lib.call("kd_image_u8hwc_to_f32chw_batch", P(img8), P(img), B, H, W, s)
+            if augment is not None:
+                _augment_image_launch(augment, params, img, s)
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
 
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
@@ -414,11 +499,16 @@ class DeviceBatchLoader:
 
     `device_resize` (None: the dataset's own setting): the workers only decode and the full-size uint8 frames are
     resized on the device (kd_image_resize_bilinear_batch, Pillow's bytes); the pinned staging set then holds the
-    full-size frames of a batch (6.2 MB per 1920x1080 frame)."""
+    full-size frames of a batch (6.2 MB per 1920x1080 frame).
+
+    `augment` (an `Augment`, its parse string, or None = off): training loaders only -- on a validation loader it is a
+    KDError.  Every batch is then transformed on the device (see the module docstring), on either path, each frame by
+    the row that `frame_params` draws for (`sample_seed`, (epoch << 32) | dataset index): a new transform every epoch, the
+    same one whenever the triple recurs.  Off: no extra launch, copy or bit."""
 
     def __init__(self, ds: PandaSetDataset, batch_size: int, shuffle: bool, num_workers: int, to_cpu: bool = False,
                  rank: int = 0, world: int = 1, train: bool = None, prefetch: int = 0, sample_seed: int = 0,
-                 device_resize: bool = None):
+                 device_resize: bool = None, augment=None):
         if prefetch < 0:
             raise KDError(f"prefetch must be >= 0, got {prefetch}")
         if device_resize is not None:            # None: as the dataset was built; the workers' load_raw reads the flag
@@ -431,6 +521,9 @@ class DeviceBatchLoader:
         self._side = self._staging = None
         self._ws = [None]
         train = shuffle if train is None else train
+        if augment is not None and not train:
+            raise KDError("augment is for training loaders only: a validation loader never augments")
+        self.augment = as_augment(augment)
         self._sampler = None
         if world > 1:
             self._sampler = RankShardSampler(len(ds), rank, world, shuffle=shuffle, equal=train)
@@ -455,10 +548,17 @@ class DeviceBatchLoader:
             yield from self._iter_prefetch(self._epoch)
             return
         for raws in self._loader:
-            b = self.dataset.prepare_batch(raws)
+            if self.augment is None:
+                b = self.dataset.prepare_batch(raws)
+            else:
+                b = self.dataset.prepare_batch(raws, self.augment, self._frame_keys(self._epoch, raws), self.sample_seed)
             if self.to_cpu:                 # for host-side analysis scripts that call .numpy() on the batch tensors
                 b = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in b.items()}
             yield b
+
+    @staticmethod
+    def _frame_keys(epoch: int, raws) -> List[int]:
+        return [(epoch << 32) | (int(r["index"]) & 0xFFFFFFFF) for r in raws]
 
     def _deliver(self, item):
         """Hand a batch prepared on the side stream to the caller's current stream."""
@@ -481,8 +581,9 @@ class DeviceBatchLoader:
         side, inflight, k = self._side, deque(), 0
         try:
             for raws in self._loader:
-                keys = [(epoch << 32) | (int(r["index"]) & 0xFFFFFFFF) for r in raws]
-                b = self.dataset.prepare_batch_staged(raws, self._staging[k % self.prefetch], side, keys, self.sample_seed, self._ws)
+                keys = self._frame_keys(epoch, raws)
+                b = self.dataset.prepare_batch_staged(raws, self._staging[k % self.prefetch], side, keys, self.sample_seed, self._ws,
+                                                      augment=self.augment)
                 ready = torch.cuda.Event()
                 ready.record(side)
                 inflight.append((b, ready))
@@ -564,29 +665,38 @@ class SyntheticRawPandaSet(PandaSetDataset):
 
 def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: List[str], batch_size: int = 4,
                                 num_workers: int = 0, verbose: bool = True, to_cpu: bool = None, prefetch: int = None,
-                                device_resize: bool = None):
+                                device_resize: bool = None, augment=None):
     """Reference signature (pandaset_dataset.py:144-160) plus `to_cpu`: batches stay on the GPU by default (the trainers'
     `.to(device)` is then free); to_cpu=True (or KD_LOADER_TO_CPU=1) returns host tensors for the reference's analysis
     scripts, which call `.numpy()` on them (test_dataset_distribution.py:22, verify_2class_distribution.py).
     `prefetch` (None: KD_LOADER_PREFETCH, default 0): batches prepared ahead of the step on a side stream, see
     DeviceBatchLoader; KD_LOADER_SAMPLE_SEED seeds its device sampler.  `device_resize` (None: KD_LOADER_DEVICE_RESIZE=1,
-    default off): the workers only decode and the bilinear resize runs on the device with Pillow's bytes."""
+    default off): the workers only decode and the bilinear resize runs on the device with Pillow's bytes.  `augment` (an
+    `Augment`, or its parse form "rot=5,flip=0.5,..."; None: KD_LOADER_AUGMENT, empty or unset = off): opt-in training
+    augmentation on the device, see DeviceBatchLoader; it goes to the TRAINING loader only.  The synthetic fallback serves
+    ready-made tensors and ignores the setting."""
     if to_cpu is None:
         to_cpu = os.environ.get("KD_LOADER_TO_CPU") == "1"
     if prefetch is None:
         prefetch = int(os.environ.get("KD_LOADER_PREFETCH", "0"))
     if device_resize is None:
         device_resize = os.environ.get("KD_LOADER_DEVICE_RESIZE") == "1"
+    if augment is None:
+        augment = os.environ.get("KD_LOADER_AUGMENT", "")
+    augment = as_augment(augment)
     pf = {"prefetch": prefetch, "sample_seed": int(os.environ.get("KD_LOADER_SAMPLE_SEED", "0"))}
     # under torch.distributed (one process per GPU) the FRAMES are sharded over ranks, equal counts per rank for training
     rank, world = _dist_rank_world()
     if os.path.isdir(root):
         train_ds = PandaSetDataset(root, train_scenes, verbose=verbose, device_resize=device_resize)
         val_ds = PandaSetDataset(root, val_scenes, verbose=verbose, device_resize=device_resize)
-        return (DeviceBatchLoader(train_ds, batch_size, shuffle=True, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf),
+        return (DeviceBatchLoader(train_ds, batch_size, shuffle=True, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world,
+                                  augment=augment, **pf),
                 DeviceBatchLoader(val_ds, batch_size, shuffle=False, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf))
     if verbose:
         print(f"[data] '{root}' not found: serving synthetic PandaSet-shaped frames")
+        if augment is not None:
+            print("[data] the synthetic frames are ready-made tensors: the augment setting is ignored")
     train = SyntheticPandaSet(n_frames=max(8, 8 * len(train_scenes)), seed=1)
     val = SyntheticPandaSet(n_frames=max(4, 4 * len(val_scenes)), seed=2)
     if world > 1:

@@ -1,6 +1,8 @@
 """Concat-fusion PandaSet training -- same entry point as the reference's train_pandaset.py
 (3-class head, class weights [0.39, 2.61, 33.09], 30 epochs, interactive resume prompt:
-train_pandaset.py:79-163), on the MI355X-native path.  KD_DATA_ROOT overrides the dataset root."""
+train_pandaset.py:79-163), on the MI355X-native path.  KD_DATA_ROOT overrides the dataset root.
+KD_LOADER_AUGMENT="rot=5,flip=0.5,jitter=0.02,..." turns the opt-in training augmentation on (training loader only;
+create_pandaset_dataloaders reads it, nothing changes here)."""
 import os
 
 import torch

@@ -14,6 +14,8 @@ Launch with `python -m torch.distributed.run --nproc-per-node N` for data-parall
 frames sharded over ranks in equal counts (every rank runs the same number of steps), rank 0's initial weights
 broadcast, gradients all-reduced in buckets during backward (CE and KD training alike), BatchNorm statistics per
 rank while training and rank 0's for validation, metrics summed over ranks, files written by rank 0 only.
+KD_LOADER_AUGMENT="rot=5,flip=0.5,jitter=0.02,..." turns the opt-in training augmentation on (training loader only;
+create_pandaset_dataloaders reads it, nothing changes here).
 """
 import json
 import os

@@ -19,6 +19,9 @@ size written to a temporary directory, with and without the host resize.
 
   ref   : B = 4,   169 000-point sweeps, max_points = 5 000   (the reference's own shape)
   bench : B = 256, 169 000-point sweeps, max_points = 80 000  (the benchmarked shape; weighted student, concat teacher)
+
+`--augment SPEC` turns the opt-in training augmentation on in the loader-fed loops (profiles/augment_kernels.txt is a
+kernel trace of such a run).
 """
 import argparse
 import os
@@ -69,7 +72,8 @@ def run_shape(name, args, out):
         return (time.perf_counter() - t0) / args.steps * 1e3
 
     def fed(prefetch, src=None):
-        loader = DeviceBatchLoader(src or ds, B, shuffle=False, num_workers=0, prefetch=prefetch, sample_seed=1)
+        loader = DeviceBatchLoader(src or ds, B, shuffle=False, num_workers=0, prefetch=prefetch, sample_seed=1,
+                                   train=True if args.augment else None, augment=args.augment or None)
         it, gaps, t0, t_host = iter(loader), [], None, 0.0
         for k in range(n_batches):
             if k == args.warmup:
@@ -190,6 +194,8 @@ def main():
     ap.add_argument("--device-resize", action="store_true", help="add the device_resize=True loop over full-size frames and its sections")
     ap.add_argument("--source-size", default="1920x1080", help="WIDTHxHEIGHT of the full-size camera frames")
     ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--augment", default="", help="KD_LOADER_AUGMENT form, e.g. rot=5,flip=0.5,jitter=0.02: the loader-fed rows "
+                    "then run the two augmentation kernels per batch (a kernel trace of such a run gives their per-launch times)")
     ap.add_argument("--out", default=None, help="also write the table to this file")
     args = ap.parse_args()
     args.prefetch = [int(v) for v in args.prefetch.split(",")]
@@ -198,6 +204,8 @@ def main():
         raise SystemExit("bench_loader.py needs an MI355X: the product path has no CPU fallback")
     out = ["KD step fed by DeviceBatchLoader over SyntheticRawPandaSet (decode and unpickle excluded: raw frames served from memory)",
            f"device: {torch.cuda.get_device_name(0)}; concat teacher -> weighted student, image 3x256x256, BEV 64x64; times in ms", ""]
+    if args.augment:
+        out.insert(2, f"loader-fed rows with augment = {args.augment}")
     if args.device_resize:
         out.insert(2, f"rows `+dr`: {args.source_size[0]}x{args.source_size[1]} frames from memory, resized on the device (device_resize=True)")
         resize_kernel_section(args, out)
