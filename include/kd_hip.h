@@ -200,6 +200,12 @@ int kd_bf16_lidar_mlp_scatter(const float* pts, const int* cell, const int* p_de
                                const float* sc0, const float* sh0, const float* W1, const float* bias1, const float* sc1,
                                const float* sh1, const float* W2, const float* bias2, const float* sc2, const float* sh2,
                                float* grid, int64_t ncells, int64_t P, int C0, int C1, int C2, void* stream);
+/* Activation contract of every scatter-max entry point: the FORWARD forms (kd_lidar_scatter_max_fwd, _scatter_max_idx_fwd,
+ * _seg_max_fwd, _seg_hold_fwd, _l2_fwd_scatter) take KD_ACT_RELU or KD_ACT_RELU6 (anything else: KD_ERR_ARG -- the zeroed grid
+ * is the maximum's identity only for non-negative values).  The BACKWARD forms (kd_lidar_scatter_max_bwd, _seg_max_bwd,
+ * _seg_share_bwd, _seg_hold_bwd, _l2_dgrad, _l2_wgrad, _l2_bwd) split dout evenly among the holders v > 0 && v == max, which is
+ * the derivative under ReLU only: under ReLU6 a maximum saturated at 6.0 has derivative 0 (ATen: the amax split, then
+ * hardtanh_backward zeroes z >= 6), so they refuse KD_ACT_RELU6 with KD_ERR_ARG instead of returning a wrong gradient. */
 int kd_lidar_scatter_max_fwd(const float* pts, const float* y, const float* sc, const float* sh, int act,
                              float* grid, int B, int64_t N, int C, int H, int W, float x0, float x1, float y0,
                              float y1, void* stream);

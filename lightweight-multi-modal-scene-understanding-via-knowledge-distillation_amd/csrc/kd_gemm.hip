@@ -1057,6 +1057,7 @@ int kd_lidar_l2_dgrad(const float* Y2, int64_t ldy2, const int* rows, const floa
                       int N2, int K1, void* stream) {
   KD_REQUIRE(Y2 && rows && grid && share && al && be && ga && sc2 && sh2 && Wt && G1 && Y1 && sc1 && sh1 && mean1 && invstd1 && partial && M > 0,
              KD_ERR_ARG, "kd_lidar_l2_dgrad: bad args");
+  KD_REQUIRE(act2 != KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_l2_dgrad: ReLU6 is not supported in the scatter-max backward (a saturated maximum has derivative 0; the holder split here is ReLU's)");
   KD_REQUIRE(M < (int64_t)1 << 31 && N2 % 4 == 0 && K1 % 4 == 0 && ldy2 % 4 == 0 && ldg1 % 4 == 0 && ldy1 % 4 == 0 && N2 >= 4, KD_ERR_SHAPE,
              "kd_lidar_l2_dgrad: channel counts and strides must be multiples of 4");
   KD_REQUIRE(kd_aligned16(Y2) && kd_aligned16(grid) && kd_aligned16(share) && kd_aligned16(Wt) && kd_aligned16(G1) && kd_aligned16(Y1),
@@ -1073,6 +1074,7 @@ int kd_lidar_l2_wgrad(const float* Y2, int64_t ldy2, const int* rows, const floa
                       void* ws, size_t ws_bytes, void* stream) {
   KD_REQUIRE(Y2 && rows && grid && share && al && be && ga && sc2 && sh2 && Y1 && sc1 && sh1 && dW && ws && M > 0, KD_ERR_ARG,
              "kd_lidar_l2_wgrad: bad args");
+  KD_REQUIRE(act2 != KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_l2_wgrad: ReLU6 is not supported in the scatter-max backward (a saturated maximum has derivative 0; the holder split here is ReLU's)");
   KD_REQUIRE(M < (int64_t)1 << 31 && N2 % 4 == 0 && K1 % 4 == 0 && ldy2 % 4 == 0 && ldy1 % 4 == 0, KD_ERR_SHAPE,
              "kd_lidar_l2_wgrad: N, K, ld must be multiples of 4");
   KD_REQUIRE(kd_aligned16(Y2) && kd_aligned16(grid) && kd_aligned16(share) && kd_aligned16(Y1) && kd_aligned16(ws), KD_ERR_ALIGN,

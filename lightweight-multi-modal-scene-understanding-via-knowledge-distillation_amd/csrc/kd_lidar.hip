@@ -297,6 +297,7 @@ int kd_lidar_scatter_max_bwd(const float* pts, const float* y, const float* sc, 
                              float* partial, int B, int64_t N, int C, int H, int W, float x0, float x1, float y0,
                              float y1, void* ws, size_t ws_bytes, void* stream) {
   KD_REQUIRE(pts && y && sc && sh && grid && dout && mean && invstd && G && partial && ws, KD_ERR_ARG, "kd_lidar_scatter_max_bwd: bad args");
+  KD_REQUIRE(act != KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_scatter_max_bwd: ReLU6 is not supported in the scatter-max backward (a saturated maximum has derivative 0; the holder split here is ReLU's)");
   const size_t need = (size_t)B * H * W * C * sizeof(unsigned);
   KD_REQUIRE(ws_bytes >= need, KD_ERR_WORKSPACE, "kd_lidar_scatter_max_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
@@ -1203,6 +1204,7 @@ int kd_lidar_seg_max_bwd(const float* y, const float* sc, const float* sh, int a
                          const int* row_of_point, float* G, float* partial, int64_t P, int64_t ncells, int C, void* stream) {
   KD_REQUIRE(y && sc && sh && grid && dout && mean && invstd && seg_start && row_of_point && G && partial && P > 0 && ncells > 0,
              KD_ERR_ARG, "kd_lidar_seg_max_bwd: bad args");
+  KD_REQUIRE(act != KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_seg_max_bwd: ReLU6 is not supported in the scatter-max backward (a saturated maximum has derivative 0; the holder split here is ReLU's)");
   KD_REQUIRE(C == 64 || C == 128 || C == 256, KD_ERR_SHAPE, "kd_lidar_seg_max_bwd: C must be 64, 128 or 256 (got %d)", C);
   SegArgs a{y, sc, sh, act, seg_start, perm, const_cast<float*>(grid), dout, mean, invstd, G, partial, ncells, C, 0, nullptr, nullptr, 0};
   const dim3 gr(seg_grid(ncells)), bl(256);
@@ -1227,6 +1229,7 @@ int kd_lidar_seg_share_bwd(const float* y, const float* sc, const float* sh, int
                            float* cnt_ws, float* partial, int64_t P, int64_t ncells, int C, void* stream) {
   KD_REQUIRE(y && sc && sh && grid && dout && mean && invstd && seg_start && row_sorted && share && cnt_ws && partial && ncells > 0 && P > 0,
              KD_ERR_ARG, "kd_lidar_seg_share_bwd: bad args");
+  KD_REQUIRE(act != KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_seg_share_bwd: ReLU6 is not supported in the scatter-max backward (a saturated maximum has derivative 0; the holder split here is ReLU's)");
   KD_REQUIRE(C == 64 || C == 128 || C == 256, KD_ERR_SHAPE, "kd_lidar_seg_share_bwd: C must be 64, 128 or 256 (got %d)", C);
   SegArgs a{y, sc, sh, act, seg_start, nullptr, const_cast<float*>(grid), dout, mean, invstd, share, partial, ncells, C,
             SEG_LONG, row_sorted, cnt_ws, seg_grid(ncells)};
@@ -1283,6 +1286,7 @@ int kd_lidar_seg_hold_bwd(const float* y, const float* sc, const float* sh, int 
                           void* stream) {
   KD_REQUIRE(y && sc && sh && grid && rawmax && holders && dout && mean && invstd && seg_start && row_sorted && share && cnt_ws &&
              partial && ncells > 0 && P > 0, KD_ERR_ARG, "kd_lidar_seg_hold_bwd: bad args");
+  KD_REQUIRE(act != KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_seg_hold_bwd: ReLU6 is not supported in the scatter-max backward (a saturated maximum has derivative 0; the holder split here is ReLU's)");
   KD_REQUIRE(C == 64 || C == 128 || C == 256, KD_ERR_SHAPE, "kd_lidar_seg_hold_bwd: C must be 64, 128 or 256 (got %d)", C);
   KD_REQUIRE((uintptr_t)holders % 4 == 0, KD_ERR_ARG, "kd_lidar_seg_hold_bwd: holders must be 4-byte aligned");
   SegArgs a{y, sc, sh, act, seg_start, nullptr, const_cast<float*>(grid), dout, mean, invstd, share, partial, ncells, C,

@@ -1,6 +1,8 @@
 """Scatter-max backward from the holder tables (kd_lidar_seg_hold_fwd / kd_lidar_seg_hold_bwd) against the two-sweep pair
 (kd_lidar_seg_max_fwd / kd_lidar_seg_share_bwd), through the C ABI, BIT FOR BIT: the same grid, the same share table and the
 same BatchNorm-backward partial sums, every row of them.  Everything here is exact; no tolerance appears.
+(The two-sweep pair is itself bit-identical to the atomic pair, test_gpu_lidar_segments.py, which -- like the holder-table
+path on the scenes below -- is pinned to an independent reference in test_gpu_lidar_kernels.py.)
 
 The contract covers finite features: a NaN / Inf feature is outside it (the two-sweep pair itself turns one into a NaN sum),
 so the scenes put non-finite values into the point COORDINATES only (those points are out of range and never scattered).

@@ -1,6 +1,7 @@
 """Cell-sorted (segmented) scatter-max against the atomic scatter-max entry points, through the C ABI.
 Both implement lidar_encoder.py:57-99 (BEV binning + amax + the even tie split of its backward); the
-atomic pair is already pinned to the oracle and the golden vectors (test_gpu_parity.py / test_gpu_units.py),
+atomic pair is pinned to an independent reference bit for bit (test_gpu_lidar_kernels.py: exact ties, long cells, NaN
+coordinates, rectangular grids) and to the oracle and the golden vectors (test_gpu_parity.py / test_gpu_units.py),
 so here the two are compared with each other BIT FOR BIT on inputs built to hit the awkward cases:
 exact ties (duplicated points), empty cells, out-of-range and NaN points, a padded tail that lands
 thousands of points in one cell, every supported width."""
