@@ -227,11 +227,22 @@ int kd_lidar_cell_sort(const float* pts, int B, int64_t N, int H, int W, float x
 /* the same bins with a deterministic in-cell order (ascending point id), applied to the POINTS: the point MLP then runs
  * on pts_sorted, every grid row owns a contiguous row range (pass perm = NULL to kd_lidar_seg_max_*), the out-of-range
  * points are the tail, and the eval path's compacted list is the first seg_start[B*H*W] rows.  perm may be NULL.
- * KD_ERR_SHAPE (-4) when H*W + 1 > 36865 (144 KB LDS histogram): fall back to kd_lidar_cell_sort. */
+ * KD_ERR_SHAPE (-4) when H*W + 1 > 36865 (144 KB LDS histogram): call kd_lidar_sort_points_wide (below) instead. */
 size_t kd_lidar_sort_points_ws_bytes(int B, int64_t N, int H, int W);
 int kd_lidar_sort_points(const float* pts, int B, int64_t N, int H, int W, float x0, float x1, float y0, float y1,
                          float* pts_sorted, int* row_sorted, int* seg_start, int* perm, void* ws, size_t ws_bytes,
                          void* stream);
+/* kd_lidar_sort_points for larger grids: same arguments, same outputs (the unique stable sort by (frame, cell); out-of-range
+ * and NaN points after all in-range points, frame by frame in original order; point bits unchanged; perm may be NULL), for
+ * any 1 <= H, W <= 4096 (KD_ERR_SHAPE beyond; B*N and B*H*W + 1 below 2^31 as above).  A two-digit counting sort inside each
+ * frame (by column, then by row): LDS holds max(H, W) + 1 ints and the workspace blocks x (W + H + 1) table entries instead of
+ * blocks x (H*W + 1) -- about 0.37 GB at B = 256, N = 80000, 256 x 256.  Small grids are accepted too (same bits as
+ * kd_lidar_sort_points; kdrt keeps that one for grids up to 192 x 192).  No floating-point atomics; the per-cell counts
+ * are integer atomic adds of ones, the same in every order. */
+size_t kd_lidar_sort_points_wide_ws_bytes(int B, int64_t N, int H, int W);
+int kd_lidar_sort_points_wide(const float* pts, int B, int64_t N, int H, int W, float x0, float x1, float y0, float y1,
+                              float* pts_sorted, int* row_sorted, int* seg_start, int* perm, void* ws, size_t ws_bytes,
+                              void* stream);
 /* Training backward of the last point-MLP layer WITHOUT the [points, C] scatter-max gradient (rows sorted by
  * kd_lidar_sort_points).  kd_lidar_seg_share_bwd leaves share[cells, C] = dout / holders and the BatchNorm-backward sums;
  * the two GEMMs rebuild G[m][c] = (rows[m] >= 0 && v > 0 && v == grid[rows[m]][c]) ? share[rows[m]][c] : 0 on load

@@ -598,6 +598,147 @@ __global__ void stable_fill_kernel(const float* __restrict__ pts, const int* __r
   if (perm) perm[pos] = (int)p;
 }
 
+// ---- the same sort for grids whose H*W + 1 bins do not fit in LDS --------------------------------
+// Two-digit least-significant-digit counting sort inside each frame: pass 0 ranks the points stably by column
+// (cell % W, W bins), pass 1 ranks pass 0's order stably by row (cell / W, plus one bin H for the out-of-range points),
+// which leaves each frame sorted by (cell, original id) with its out-of-range points last, in original order.  Each
+// pass is stable_count_kernel's scheme with max(H, W) + 1 bins: block-local stable rank (in-wave rank by shuffle, the 16
+// waves take turns on the LDS histogram), the histogram to T[frame][block][digit], a per-(frame, digit) exclusive prefix
+// over the blocks and a per-frame exclusive scan of the digit totals.  Between the passes only (original id, cell)
+// travel; the points are gathered once, by the final scatter.  seg_start is the scan of integer per-cell counts (one
+// integer atomicAdd per distinct cell per wave: a sum of ones, the same in every order).  The tables hold
+// blocks x (W + H + 1) ints instead of blocks x (H*W + 1).
+constexpr int WIDE_MAX_DIM = 4096;
+
+// lanes of this wave holding the same key: `below` of them in lower lanes, `all` in total (this lane included)
+__device__ __forceinline__ void wave_same_key(int key, int lane, int& below, int& all) {
+  below = 0; all = 0;
+#pragma unroll 16
+  for (int j = 0; j < 64; ++j) {
+    const int kj = __shfl(key, j);
+    all += kj == key ? 1 : 0;
+    below += (kj == key && j < lane) ? 1 : 0;
+  }
+}
+
+// stable rank of this thread's key inside the 1024-thread block; hist (zeroed by the caller, before a barrier) ends up
+// holding the block's histogram
+__device__ __forceinline__ int block_stable_rank(int key, bool act, int below, int all, int* hist) {
+  const int wave = threadIdx.x >> 6;
+  int lr = 0;
+  for (int w = 0; w < SORT_BLK / 64; ++w) {
+    if (wave == w && act) lr = hist[key] + below;
+    __syncthreads();
+    if (wave == w && act && below == all - 1) hist[key] += all;      // the last lane of each key group
+    __syncthreads();
+  }
+  return lr;
+}
+
+// PASS 0: reads the points in original order, writes cell[p] (or -1), the column rank and the per-cell counts.
+// PASS 1: reads mid_cell (pass 0's order), writes the row rank.  nd = W (pass 0) or H + 1 (pass 1) bins.
+template <int PASS>
+__global__ __launch_bounds__(SORT_BLK) void wide_count_kernel(const float* __restrict__ pts, int* __restrict__ cell_io,
+                                                              int* __restrict__ lrank_out, int* __restrict__ T,
+                                                              int* counts, int64_t N, int nblk, BevGeom g) {
+  extern __shared__ int hist[];
+  const int nd = PASS == 0 ? g.W : g.H + 1;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int b = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+  for (int i = tid; i < nd; i += SORT_BLK) hist[i] = 0;
+  const int64_t n = (int64_t)blk * SORT_BLK + tid;
+  const bool act = n < N;
+  const int64_t p = (int64_t)b * N + (act ? n : 0);
+  int cell = -1;
+  if (act) {
+    if (PASS == 0) bev_cell(kd_ld4(pts + p * 4), g, cell); else cell = cell_io[p];
+  }
+  // out-of-range points: column 0 (any fixed column keeps their order), row H (behind every in-range point)
+  const int key = !act ? -1 : PASS == 0 ? (cell >= 0 ? cell % g.W : 0) : (cell >= 0 ? cell / g.W : g.H);
+  int below, all;
+  wave_same_key(key, lane, below, all);
+  if (PASS == 0) {
+    int cbelow, call;
+    wave_same_key(cell, lane, cbelow, call);
+    if (cell >= 0 && cbelow == 0) atomicAdd(counts + (int64_t)b * g.H * g.W + cell, call);
+  }
+  __syncthreads();
+  const int lr = block_stable_rank(key, act, below, all, hist);
+  if (act) {
+    if (PASS == 0) cell_io[p] = cell;
+    lrank_out[p] = lr;
+  }
+  int* Tb = T + ((int64_t)b * nblk + blk) * nd;
+  for (int i = tid; i < nd; i += SORT_BLK) Tb[i] = hist[i];
+}
+
+// T[b][blk][d] <- exclusive prefix over blk; totals to tot[b][d]; last_tot[b] (optional) = total of the last digit
+__global__ void wide_prefix_kernel(int* T, int* __restrict__ tot, int* __restrict__ last_tot, int B, int nblk, int nd) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)B * nd) return;
+  const int b = (int)(idx / nd), d = (int)(idx % nd);
+  int run = 0;
+  for (int blk = 0; blk < nblk; ++blk) {
+    int* t = T + ((int64_t)b * nblk + blk) * nd + d;
+    const int v = *t;
+    *t = run;
+    run += v;
+  }
+  tot[idx] = run;
+  if (last_tot && d == nd - 1) last_tot[b] = run;
+}
+
+// tot[b][0 .. nd) <- its exclusive prefix, in place: one wave per frame, 64 digits at a time with a carry
+__global__ __launch_bounds__(64) void wide_frame_scan_kernel(int* tot, int nd) {
+  int* t = tot + (int64_t)blockIdx.x * nd;
+  const int lane = threadIdx.x;
+  int carry = 0;
+  for (int base = 0; base < nd; base += 64) {
+    const int i = base + lane;
+    const int v = i < nd ? t[i] : 0;
+    int incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int u = __shfl_up(incl, off);
+      if (lane >= off) incl += u;
+    }
+    if (i < nd) t[i] = carry + incl - v;
+    carry += __shfl(incl, 63);
+  }
+}
+
+// pass 0's scatter: (original id, cell) to their place in the frame's column order
+__global__ void wide_mid_kernel(const int* __restrict__ cell, const int* __restrict__ lrank, const int* __restrict__ T,
+                                const int* __restrict__ off, int* __restrict__ mid_id, int* __restrict__ mid_cell, int64_t P,
+                                int64_t N, int nblk, int W) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  const int b = (int)(p / N), blk = (int)((p % N) / SORT_BLK), c = cell[p];
+  const int d = c >= 0 ? c % W : 0;
+  const int64_t pos = (int64_t)b * N + off[(int64_t)b * W + d] + T[((int64_t)b * nblk + blk) * W + d] + lrank[p];
+  mid_id[pos] = (int)p;
+  mid_cell[pos] = c;
+}
+
+// pass 1's scatter: the in-range points of frame b start at seg_start[b*HW] (all in-range points come first, frame by
+// frame), its out-of-range points at inv_base[b]
+__global__ void wide_fill_kernel(const float* __restrict__ pts, const int* __restrict__ mid_id, const int* __restrict__ mid_cell,
+                                 const int* __restrict__ lrank, const int* __restrict__ T, const int* __restrict__ off,
+                                 const int* __restrict__ seg_start, const int* __restrict__ inv_base,
+                                 float* __restrict__ pts_sorted, int* __restrict__ row_sorted, int* __restrict__ perm,
+                                 int64_t P, int64_t N, int nblk, int H, int W) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= P) return;
+  const int b = (int)(q / N), blk = (int)((q % N) / SORT_BLK), c = mid_cell[q], p = mid_id[q];
+  const int nd = H + 1, d = c >= 0 ? c / W : H;
+  const int64_t HW = (int64_t)H * W;
+  const int in_digit = T[((int64_t)b * nblk + blk) * nd + d] + lrank[q];
+  const int64_t pos = c >= 0 ? (int64_t)seg_start[b * HW] + off[(int64_t)b * nd + d] + in_digit : (int64_t)inv_base[b] + in_digit;
+  kd_st4(pts_sorted + pos * 4, kd_ld4(pts + (int64_t)p * 4));
+  row_sorted[pos] = c >= 0 ? (int)(b * HW + c) : -1;
+  if (perm) perm[pos] = p;
+}
+
 struct SegArgs {
   const float* y; const float* sc; const float* sh; int act;          // deferred [P, C]
   const int* start; const int* perm;                                  // [ncells + 1], [P]
@@ -1118,7 +1259,7 @@ size_t kd_lidar_sort_points_ws_bytes(int B, int64_t N, int H, int W) {
 // Stable sort of the points by (frame, cell); out-of-range points go to the end (frame by frame, original order).
 //   pts_sorted[B*N, 4]; row_sorted[B*N] = grid row of each sorted point or -1; seg_start[B*H*W + 1] as in
 //   kd_lidar_cell_sort (seg_start[B*H*W] = number of in-range points); perm (optional, may be NULL): sorted -> original id.
-// Returns KD_ERR_SHAPE when H*W + 1 exceeds the LDS histogram (callers fall back to kd_lidar_cell_sort).
+// Returns KD_ERR_SHAPE when H*W + 1 exceeds the LDS histogram (callers take kd_lidar_sort_points_wide for such a grid).
 int kd_lidar_sort_points(const float* pts, int B, int64_t N, int H, int W, float x0, float x1, float y0, float y1,
                          float* pts_sorted, int* row_sorted, int* seg_start, int* perm, void* ws, size_t ws_bytes,
                          void* stream) {
@@ -1154,6 +1295,58 @@ int kd_lidar_sort_points(const float* pts, int B, int64_t N, int H, int W, float
   hipLaunchKernelGGL(stable_fill_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, pts, key, lrank, T, seg_start, inv,
                      pts_sorted, row_sorted, perm, P, N, nblk, HW);
   return kd_check_launch("kd_lidar_sort_points");
+}
+
+size_t kd_lidar_sort_points_wide_ws_bytes(int B, int64_t N, int H, int W) {
+  const int64_t P = (int64_t)B * N, nblk = (N + SORT_BLK - 1) / SORT_BLK, n = (int64_t)B * H * W + 1, nd = (int64_t)W + H + 1;
+  return (size_t)(4 * P + (int64_t)B * nblk * nd + (int64_t)B * nd + B + (n + SCAN_CHUNK - 1) / SCAN_CHUNK) * sizeof(int);
+}
+
+// kd_lidar_sort_points for any grid up to 4096 x 4096: same arguments, same outputs (the unique stable sort by
+// (frame, cell), out-of-range points last), LDS bounded by max(H, W) + 1 ints, workspace without a blocks x H*W term.
+int kd_lidar_sort_points_wide(const float* pts, int B, int64_t N, int H, int W, float x0, float x1, float y0, float y1,
+                              float* pts_sorted, int* row_sorted, int* seg_start, int* perm, void* ws, size_t ws_bytes,
+                              void* stream) {
+  KD_REQUIRE(pts && pts_sorted && row_sorted && seg_start && ws && B > 0 && N > 0 && H > 0 && W > 0, KD_ERR_ARG, "kd_lidar_sort_points_wide: bad args");
+  KD_REQUIRE(H <= WIDE_MAX_DIM && W <= WIDE_MAX_DIM, KD_ERR_SHAPE, "kd_lidar_sort_points_wide: grid %d x %d exceeds %d cells per side", H, W,
+             WIDE_MAX_DIM);
+  const int64_t P = (int64_t)B * N, ncells = (int64_t)B * H * W, n = ncells + 1;
+  KD_REQUIRE(P < (int64_t)INT32_MAX && n < (int64_t)INT32_MAX, KD_ERR_SHAPE, "kd_lidar_sort_points_wide: more than 2^31 points or cells");
+  KD_REQUIRE(ws_bytes >= kd_lidar_sort_points_wide_ws_bytes(B, N, H, W), KD_ERR_WORKSPACE, "kd_lidar_sort_points_wide: workspace too small");
+  const int nblk = (int)((N + SORT_BLK - 1) / SORT_BLK);
+  KD_REQUIRE((int64_t)B * nblk < (int64_t)INT32_MAX, KD_ERR_SHAPE, "kd_lidar_sort_points_wide: too many blocks");
+  hipStream_t st = (hipStream_t)stream;
+  const int nd0 = W, nd1 = H + 1;
+  int* cell = (int*)ws;                       // [P] original order
+  int* lrank = cell + P;                      // [P] column rank, then row rank
+  int* mid_id = lrank + P;                    // [P] pass 0's order
+  int* mid_cell = mid_id + P;                 // [P]
+  int* T0 = mid_cell + P;                     // [B][nblk][W]
+  int* T1 = T0 + (int64_t)B * nblk * nd0;     // [B][nblk][H + 1]
+  int* off0 = T1 + (int64_t)B * nblk * nd1;   // [B][W]
+  int* off1 = off0 + (int64_t)B * nd0;        // [B][H + 1]
+  int* inv = off1 + (int64_t)B * nd1;         // [B]
+  int* bsum = inv + B;
+  const int nsb = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
+  const BevGeom g{x0, x1 - x0, y0, y1 - y0, H, W};
+  hipError_t e = hipMemsetAsync(seg_start, 0, (size_t)n * sizeof(int), st);
+  KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_sort_points_wide: memset failed: %s", hipGetErrorString(e));
+  const dim3 blocks((unsigned)(B * nblk)), per_point((unsigned)((P + 255) / 256));
+  hipLaunchKernelGGL(wide_count_kernel<0>, blocks, dim3(SORT_BLK), (size_t)nd0 * sizeof(int), st, pts, cell, lrank, T0, seg_start, N, nblk, g);
+  hipLaunchKernelGGL(wide_prefix_kernel, dim3((unsigned)(((int64_t)B * nd0 + 255) / 256)), dim3(256), 0, st, T0, off0, (int*)nullptr, B, nblk, nd0);
+  hipLaunchKernelGGL(wide_frame_scan_kernel, dim3(B), dim3(64), 0, st, off0, nd0);
+  hipLaunchKernelGGL(wide_mid_kernel, per_point, dim3(256), 0, st, cell, lrank, T0, off0, mid_id, mid_cell, P, N, nblk, W);
+  hipLaunchKernelGGL(wide_count_kernel<1>, blocks, dim3(SORT_BLK), (size_t)nd1 * sizeof(int), st, (const float*)nullptr, mid_cell, lrank, T1,
+                     (int*)nullptr, N, nblk, g);
+  hipLaunchKernelGGL(wide_prefix_kernel, dim3((unsigned)(((int64_t)B * nd1 + 255) / 256)), dim3(256), 0, st, T1, off1, inv, B, nblk, nd1);
+  hipLaunchKernelGGL(wide_frame_scan_kernel, dim3(B), dim3(64), 0, st, off1, nd1);
+  hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nsb), dim3(256), 0, st, seg_start, bsum, n);
+  hipLaunchKernelGGL(scan_bsums_kernel, dim3(1), dim3(1024), 0, st, bsum, nsb);
+  hipLaunchKernelGGL(scan_apply_kernel, dim3(nsb), dim3(256), 0, st, seg_start, bsum, n);
+  hipLaunchKernelGGL(stable_inv_base_kernel, dim3(1), dim3(64), 0, st, seg_start, inv, B, ncells);
+  hipLaunchKernelGGL(wide_fill_kernel, per_point, dim3(256), 0, st, pts, mid_id, mid_cell, lrank, T1, off1, seg_start, inv, pts_sorted,
+                     row_sorted, perm, P, N, nblk, H, W);
+  return kd_check_launch("kd_lidar_sort_points_wide");
 }
 
 // out_pts[i] = pts[perm[i]], out_row[i] = row_of_point[perm[i]] for i < *nvalid_dev (= seg_start[B*H*W]): the same

@@ -138,8 +138,9 @@ def forward_bf16(model, images: torch.Tensor, points: torch.Tensor, return_inter
     Bp, Np = points.shape[0], points.shape[1]
     r = lenc.point_cloud_range
     rng = (float(r[0]), float(r[3]), float(r[1]), float(r[4]))
-    if Hg * Wg + 1 > units.SORT_MAX_BINS:
-        raise KDError("bf16 path: BEV grids above 192 x 192 cells are not supported")
+    if not units.sorted_mode_available(Hg, Wg):
+        raise KDError("bf16 path: BEV grids above 192 x 192 cells need the wide point sort (KD_LIDAR_WIDE_SORT=0 turned it off; "
+                      "it serves up to 4096 cells per side)")
     spts, cell, seg_start = units.sort_points(pts, Bp, Np, Hg, Wg, rng)
     counter = seg_start[Bp * Hg * Wg:]
     u0, u1, u2 = lenc._units()

@@ -1121,11 +1121,22 @@ def cell_sort(pts, B, N, H, W, rng):
 
 
 SORT_MAX_BINS = 36865            # kd_lidar_sort_points: H*W + 1 histogram bins in LDS (grids up to 192 x 192)
+SORT_WIDE_MAX_DIM = 4096         # kd_lidar_sort_points_wide: cells per grid side
+# larger grids: the two-digit sort kd_lidar_sort_points_wide (default); KD_LIDAR_WIDE_SORT=0: no sorted mode above 192 x 192
+# (training and the frozen teacher bin point ids with kd_lidar_cell_sort, forward_bf16 refuses such a grid)
+_SORT_WIDE = os.environ.get("KD_LIDAR_WIDE_SORT", "1") != "0"
+
+
+def sorted_mode_available(H, W):
+    """Can sort_points serve an H x W grid?"""
+    return H * W + 1 <= SORT_MAX_BINS or (_SORT_WIDE and max(H, W) <= SORT_WIDE_MAX_DIM)
 
 
 def sort_points(pts, B, N, H, W, rng):
-    """Points stably sorted by (frame, cell) (kd_lidar_sort_points) -> (pts_sorted, row_sorted, seg_start).  Shared
-    between the frozen teacher and the student of one KD step exactly like cell_sort."""
+    """Points stably sorted by (frame, cell) (kd_lidar_sort_points; kd_lidar_sort_points_wide above 192 x 192 cells) ->
+    (pts_sorted, row_sorted, seg_start).  Shared between the frozen teacher and the student of one KD step exactly like
+    cell_sort."""
+    fn = "kd_lidar_sort_points" if H * W + 1 <= SORT_MAX_BINS else "kd_lidar_sort_points_wide"
     key = ("points", pts.data_ptr(), pts._version, B, N, H, W, tuple(float(r) for r in rng), stream())
     hit = _sort_cache.get("points") if _sort_sharing else None
     if hit is not None and hit[0] == key:
@@ -1134,9 +1145,9 @@ def sort_points(pts, B, N, H, W, rng):
     spts = torch.empty(B * N, 4, device=dev, dtype=torch.float32)
     row_sorted = torch.empty(B * N, device=dev, dtype=torch.int32)
     seg_start = torch.empty(B * H * W + 1, device=dev, dtype=torch.int32)
-    nbytes = lib.kd_lidar_sort_points_ws_bytes(B, N, H, W)
+    nbytes = getattr(lib, fn + "_ws_bytes")(B, N, H, W)
     ws = ops.workspace(nbytes, dev)
-    lib.call("kd_lidar_sort_points", P(pts), B, N, H, W, float(rng[0]), float(rng[1]), float(rng[2]), float(rng[3]),
+    lib.call(fn, P(pts), B, N, H, W, float(rng[0]), float(rng[1]), float(rng[2]), float(rng[3]),
              P(spts), P(row_sorted), P(seg_start), None, P(ws), nbytes, stream())
     out = (spts, row_sorted, seg_start)
     if _sort_sharing:
@@ -1162,10 +1173,10 @@ class LidarFn(torch.autograd.Function):
             # (no batch statistics, never scattered), so compact them away before the point MLP.
             dev = pts.device
             cpts = ccell = None
-            if _SCATTER_MODE != "sorted" or H * W + 1 > SORT_MAX_BINS:
+            if _SCATTER_MODE != "sorted" or not sorted_mode_available(H, W):
                 cpts = torch.empty(B * N, 4, device=dev, dtype=torch.float32)
                 ccell = torch.empty(B * N, device=dev, dtype=torch.int32)
-            if _SCATTER_MODE == "sorted" and H * W + 1 <= SORT_MAX_BINS:
+            if _SCATTER_MODE == "sorted" and sorted_mode_available(H, W):
                 # the head of the cell-sorted point array (shared with the student of the same step) IS the compacted
                 # list; the fused scatter epilogue merges neighbouring rows in registers before touching the grid
                 cpts, ccell, seg_start = sort_points(pts, B, N, H, W, rng)
@@ -1204,7 +1215,7 @@ class LidarFn(torch.autograd.Function):
             return ops.nchw_from_matrix(grid, (B, H, W))
         mode = "atomic"
         if units[-1].conv.weight.shape[0] in (64, 128, 256) and _SCATTER_MODE != "atomic":
-            mode = "points" if (_SCATTER_MODE == "sorted" and H * W + 1 <= SORT_MAX_BINS) else "ids"
+            mode = "points" if (_SCATTER_MODE == "sorted" and sorted_mode_available(H, W)) else "ids"
         seg = None
         cur = pts
         if mode == "points":
