@@ -510,6 +510,36 @@ int kd_grad_sumsq_partials(const float* g, int64_t n, void* ws, size_t ws_bytes,
 int kd_adamw_step_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, float* clip_state, void* ws,
                            size_t ws_bytes, float beta1, float beta2, float eps, float weight_decay, float ginv, float max_norm,
                            void* stream);
+/* Parameter groups and an EMA weight copy in the same device step.
+ * kd_adamw_step_groups_dev: kd_adamw_step_dev (clip_state == NULL and ws == NULL) or kd_adamw_step_clip_dev (both given, same
+ * clip_state, workspace, norm, skip rule and bits) where every float4 of the buffer takes lr and weight_decay from its segment:
+ *   seg_end[n_seg]   ascending segment ends in float4 units, the last = n / 4 (a padding element belongs to the tensor before it)
+ *   seg_group[n_seg] the group of each segment, < n_groups
+ *   group_state      device float[n_groups][2] = (lr, weight_decay) per group; rewrite the lr entries between graph replays
+ * seg_end / seg_group are device int32 arrays; seg_end_host / seg_group_host are the caller's host copies of the same values, which
+ * this call validates (it never reads device memory on the host).  Every workgroup copies the table into LDS and a thread searches
+ * it when its float4 leaves the segment of its previous iteration; at most 4096 segments (KD_ERR_SHAPE beyond: merge neighbouring
+ * tensors of one group).  Cost of the copy: workgroups x n_seg x 8 bytes of (mostly L2) reads per step, 1 MB at the 64 segments of
+ * the published models with 2048 workgroups, 64 MB at 4096 segments -- more than the update's own traffic there, so keep tables
+ * short.  `state` is the same float[4]; state[0] (the single learning rate) is neither read nor written.
+ * beta1, beta2, eps are shared by all groups.  Per-element arithmetic is kd_adamw_step_clip_dev's, expression for expression: with
+ * one segment the results are bit-identical to kd_adamw_step_dev / kd_adamw_step_clip_dev at that lr and weight_decay.
+ * EMA (ema == NULL and ema_state == NULL: off): ema is a float[n] copy of the weights, ema_state a device float[2] that the tick
+ * kernel writes on every applied step:
+ *   ema_state[0] = d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay     t = the step count after the tick; fp32
+ *   ema_state[1] = 1 - d_t                                                               operations, each rounded once
+ *   ema[i] = fmaf(d_t, ema[i], ema_state[1] * p_new[i])      the product rounded to fp32, then one fused multiply-add
+ * When ema_state[1] == 0 (d_t = 1) ema is not touched; when d_t == 0 p_new is stored as it is: both exact, bit for bit.
+ * A skipped step (non-finite gradient norm with clipping on) leaves p, m, v, ema, ema_state and the step count unchanged.
+ * n a positive multiple of 4 with n / 4 < 2^31, ema_decay in [0, 1], max_norm finite and > 0 when clipping, ends ascending from
+ * above 0 to n / 4, group indices in range, ema with ema_state and clip_state with ws (KD_ERR_ARG); p, g, m, v, ema 16-byte and
+ * ws 8-byte aligned (KD_ERR_ALIGN); ws_bytes >= kd_grad_sumsq_ws_bytes(n) when clipping (KD_ERR_WORKSPACE).  A refused call
+ * launches nothing. */
+int kd_adamw_step_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const int* seg_end,
+                             const int* seg_group, const int* seg_end_host, const int* seg_group_host, int n_seg,
+                             const float* group_state, int n_groups, float* ema, float* ema_state, float ema_decay, int ema_warmup,
+                             float* clip_state, void* ws, size_t ws_bytes, float beta1, float beta2, float eps, float ginv,
+                             float max_norm, void* stream);
 
 /* ---- inference-mode block fusion (csrc/kd_block.hip) ------------------------------------------------------------------
  * The tail of an InvertedResidual (reference camera_encoder.py:30-42: depthwise 3x3 + BN + ReLU6, project 1x1 + BN, + x) or a

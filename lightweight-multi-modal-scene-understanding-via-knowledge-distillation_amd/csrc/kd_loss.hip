@@ -488,3 +488,155 @@ int kd_adamw_step_clip_dev(float* p, const float* g, float* m, float* v, int64_t
 }
 
 }  // extern "C"
+
+// ---- parameter groups and an EMA weight copy in the device-state AdamW step ---------------------------------------------------
+// The flat buffer is cut into segments (ascending ends in float4 units, one group index each); a float4 never straddles two
+// tensors, so one lookup per float4 gives its group's (lr, weight_decay).  Every workgroup copies the table into LDS once and a
+// thread searches it only when its float4 leaves the segment of its previous iteration.  The EMA copy is one more 16-byte load
+// and store per float4 of parameters that are in registers anyway.
+namespace {
+
+constexpr int GROUPS_MAX_SEG = 4096;               // 32 KiB of LDS for the table
+
+// One block.  With `clip`: adamw_clip_tick_kernel, expression for expression (the same reduction, the same bits).  Without:
+// adamw_tick_kernel.  An applied step then refreshes ema[0] = d_t and ema[1] = 1 - d_t from the step count after the tick.
+__global__ __launch_bounds__(256) void adamw_groups_tick_kernel(const double* partial, int nblk, float* state, float* clip, float* ema,
+                                                                float b1, float b2, float ginv, float max_norm, float decay,
+                                                                int warmup) {
+  __shared__ double red[256];
+  bool apply = true;
+  if (clip) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nblk; i += 256) s += partial[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+      if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      const float norm = (float)((double)ginv * sqrt(red[0]));
+      clip[0] = norm;
+      apply = isfinite(norm);
+      if (apply) {
+        const float coef = fminf(1.f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)));
+        clip[1] = __fmul_rn(ginv, coef);
+        clip[3] = 1.f;
+      } else {
+        clip[1] = 0.f;
+        clip[2] = clip[2] + 1.f;
+        clip[3] = 0.f;
+      }
+    }
+  }
+  if (threadIdx.x == 0 && apply) {
+    const float t = state[1] + 1.f;                // adamw_tick_kernel
+    state[1] = t;
+    state[2] = (float)(1.0 - pow((double)b1, (double)t));
+    state[3] = (float)sqrt(1.0 - pow((double)b2, (double)t));
+    if (ema) {
+      const float d = warmup ? fminf(decay, __fdiv_rn(__fadd_rn(1.f, t), __fadd_rn(10.f, t))) : decay;
+      ema[0] = d;
+      ema[1] = __fsub_rn(1.f, d);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float* g, float* m, float* v, float* e, int64_t n4,
+                                                           const float* state, const int* seg_end, const int* seg_group, int n_seg,
+                                                           const float* group_state, const float* clip, const float* ema, float b1,
+                                                           float b2, float eps, float ginv) {
+  if (clip && clip[3] == 0.f) return;              // non-finite gradient norm: the step is skipped, nothing is written
+  extern __shared__ int tab[];
+  int* ends = tab;
+  int* grps = tab + n_seg;
+  for (int i = threadIdx.x; i < n_seg; i += 256) { ends[i] = seg_end[i]; grps[i] = seg_group[i]; }
+  __syncthreads();
+  const float bc1 = state[2], bc2sqrt = state[3], gs = clip ? clip[1] : ginv;
+  const float d = e ? ema[0] : 1.f, omd = e ? ema[1] : 0.f;
+  int64_t lo = 0, hi = 0;                          // the float4 range of the segment whose lr, wd are loaded (none yet)
+  float lr = 0.f, wd = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    if (i >= hi || i < lo) {                       // the first segment whose end lies beyond i
+      int a = 0, b = n_seg - 1;
+      while (a < b) {
+        const int c = (a + b) >> 1;
+        if ((int64_t)ends[c] > i) b = c; else a = c + 1;
+      }
+      lo = a ? ends[a - 1] : 0;
+      hi = ends[a];
+      const int gi = grps[a];
+      lr = group_state[2 * gi];
+      wd = group_state[2 * gi + 1];
+    }
+    float4 pv = kd_ld4(p + i * 4), mv = kd_ld4(m + i * 4), vv = kd_ld4(v + i * 4);
+    const float4 gv = kd_ld4(g + i * 4);
+    adamw_clip_elem(pv.x, gv.x, mv.x, vv.x, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    adamw_clip_elem(pv.y, gv.y, mv.y, vv.y, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    adamw_clip_elem(pv.z, gv.z, mv.z, vv.z, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    adamw_clip_elem(pv.w, gv.w, mv.w, vv.w, lr, bc1, bc2sqrt, b1, b2, eps, wd, gs);
+    kd_st4(p + i * 4, pv); kd_st4(m + i * 4, mv); kd_st4(v + i * 4, vv);
+    if (omd != 0.f) {                              // d == 1: the average keeps its bits, no traffic
+      float4 ev = pv;                              // d == 0: the average is the parameter, bit for bit, no load
+      if (d != 0.f) {
+        ev = kd_ld4(e + i * 4);
+        ev.x = fmaf(d, ev.x, omd * pv.x);
+        ev.y = fmaf(d, ev.y, omd * pv.y);
+        ev.z = fmaf(d, ev.z, omd * pv.z);
+        ev.w = fmaf(d, ev.w, omd * pv.w);
+      }
+      kd_st4(e + i * 4, ev);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// kd_adamw_step_dev / kd_adamw_step_clip_dev with per-segment (lr, weight_decay) and an optional EMA copy (see include/kd_hip.h).
+// Two launches (the tick, the update), three with clipping.  The table is validated here from the caller's host copy.
+int kd_adamw_step_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const int* seg_end,
+                             const int* seg_group, const int* seg_end_host, const int* seg_group_host, int n_seg,
+                             const float* group_state, int n_groups, float* ema, float* ema_state, float ema_decay, int ema_warmup,
+                             float* clip_state, void* ws, size_t ws_bytes, float beta1, float beta2, float eps, float ginv,
+                             float max_norm, void* stream) {
+  KD_REQUIRE(p && g && m && v && state && seg_end && seg_group && seg_end_host && seg_group_host && group_state && n > 0 && n % 4 == 0 &&
+                 n / 4 <= (int64_t)INT32_MAX && n_seg > 0 && n_groups > 0,
+             KD_ERR_ARG, "kd_adamw_step_groups_dev: bad args (n must be a positive multiple of 4)");
+  KD_REQUIRE((ema == nullptr) == (ema_state == nullptr), KD_ERR_ARG, "kd_adamw_step_groups_dev: ema and ema_state go together");
+  KD_REQUIRE(!ema || (ema_decay >= 0.f && ema_decay <= 1.f), KD_ERR_ARG, "kd_adamw_step_groups_dev: ema_decay must lie in [0, 1] (got %g)",
+             (double)ema_decay);
+  KD_REQUIRE((clip_state == nullptr) == (ws == nullptr), KD_ERR_ARG, "kd_adamw_step_groups_dev: clip_state and ws go together");
+  KD_REQUIRE(!clip_state || (std::isfinite(max_norm) && max_norm > 0.f), KD_ERR_ARG,
+             "kd_adamw_step_groups_dev: max_norm must be finite and > 0 (got %g)", (double)max_norm);
+  KD_REQUIRE(n_seg <= GROUPS_MAX_SEG, KD_ERR_SHAPE, "kd_adamw_step_groups_dev: %d segments, at most %d (merge neighbours of one group)",
+             n_seg, GROUPS_MAX_SEG);
+  int prev = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    KD_REQUIRE(seg_end_host[i] > prev, KD_ERR_ARG, "kd_adamw_step_groups_dev: segment ends must ascend (end[%d] = %d after %d)", i,
+               seg_end_host[i], prev);
+    KD_REQUIRE(seg_group_host[i] >= 0 && seg_group_host[i] < n_groups, KD_ERR_ARG,
+               "kd_adamw_step_groups_dev: segment %d names group %d of %d", i, seg_group_host[i], n_groups);
+    prev = seg_end_host[i];
+  }
+  KD_REQUIRE((int64_t)prev == n / 4, KD_ERR_ARG, "kd_adamw_step_groups_dev: the last segment ends at float4 %d, the buffer at %lld", prev,
+             (long long)(n / 4));
+  KD_REQUIRE(kd_aligned16(p) && kd_aligned16(g) && kd_aligned16(m) && kd_aligned16(v) && kd_aligned16(ema) &&
+                 (reinterpret_cast<uintptr_t>(ws) & 7u) == 0,
+             KD_ERR_ALIGN, "kd_adamw_step_groups_dev: p, g, m, v, ema must be 16-byte aligned, ws 8-byte aligned");
+  const int64_t nblk = gsq_blocks(n);
+  KD_REQUIRE(!clip_state || ws_bytes >= (size_t)nblk * sizeof(double), KD_ERR_WORKSPACE, "kd_adamw_step_groups_dev: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  if (clip_state) hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nblk), dim3(256), 0, st, g, n / 4, (double*)ws);
+  hipLaunchKernelGGL(adamw_groups_tick_kernel, dim3(1), dim3(256), 0, st, (const double*)ws, (int)nblk, state, clip_state, ema_state, beta1,
+                     beta2, ginv, max_norm, ema_decay, ema_warmup);
+  int64_t grid = (n / 4 + 255) / 256;
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)grid), dim3(256), (size_t)n_seg * 2 * sizeof(int), st, p, g, m, v, ema, n / 4,
+                     (const float*)state, seg_end, seg_group, n_seg, group_state, (const float*)clip_state, (const float*)ema_state, beta1,
+                     beta2, eps, ginv);
+  return kd_check_launch("kd_adamw_step_groups_dev");
+}
+
+}  // extern "C"

@@ -23,13 +23,36 @@ from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
 from kdrt.losses import RegionLoss, confusion, region_seg_loss, seg_loss
-from kdrt.optim import FusedAdamW
+from kdrt.optim import FusedAdamW, decay_groups
 
 try:
     from tqdm import tqdm
 except ImportError:  # pragma: no cover
     def tqdm(x, **kw):
         return x
+
+
+def optim_options_from_env(env=None):
+    """Trainer keywords from the entry scripts' switches: KD_EMA_DECAY=0.999, KD_EMA_WARMUP=1, KD_NO_DECAY_NORM_BIAS=1,
+    KD_LR_MULT="camera_encoder=0.1,lidar_encoder=0.5".  Nothing set: {} -- the scripts then build the trainer exactly as before."""
+    env = os.environ if env is None else env
+    kw = {}
+    if env.get("KD_EMA_DECAY"):
+        kw["ema_decay"] = float(env["KD_EMA_DECAY"])
+        kw["ema_warmup"] = env.get("KD_EMA_WARMUP") == "1"
+    elif env.get("KD_EMA_WARMUP") == "1":
+        raise ValueError("KD_EMA_WARMUP=1 needs KD_EMA_DECAY")
+    if env.get("KD_NO_DECAY_NORM_BIAS") == "1":
+        kw["no_decay_norm_bias"] = True
+    if env.get("KD_LR_MULT"):
+        mult = {}
+        for item in env["KD_LR_MULT"].split(","):
+            name, sep, val = item.partition("=")
+            if not sep or not name.strip():
+                raise ValueError(f"KD_LR_MULT must look like 'camera_encoder=0.1,head=2', got {env['KD_LR_MULT']!r}")
+            mult[name.strip()] = float(val)
+        kw["lr_mult"] = mult
+    return kw
 
 
 class SegmentationMetrics:
@@ -80,7 +103,8 @@ class SegmentationMetrics:
 
 class Trainer:
     def __init__(self, model, train_loader, val_loader, device, lr=1e-3, weight_decay=1e-3, save_dir="checkpoints",
-                 class_weights=None, num_epochs=20, max_grad_norm=None, hard_loss=None):
+                 class_weights=None, num_epochs=20, max_grad_norm=None, ema_decay=None, ema_warmup=False,
+                 no_decay_norm_bias=False, lr_mult=None, hard_loss=None):
         self.model = model
         self.train_loader = train_loader
         self.val_loader = val_loader
@@ -99,13 +123,23 @@ class Trainer:
             self.criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
         else:
             self.criterion = lambda logits, seg: region_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
-        self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        # Parameter groups (no weight decay on BatchNorm parameters and biases, a learning-rate multiplier per top-level module)
+        # and an EMA of the weights: all off by default, and the optimiser then makes exactly the calls it made before.  The
+        # flat buffer keeps the model.parameters() order whatever the grouping, so the gradient buckets stay contiguous.
+        self.ema_decay = ema_decay
+        params = model.parameters()
+        if no_decay_norm_bias or lr_mult:
+            params = decay_groups(model, lr, weight_decay, lr_mult, no_decay=bool(no_decay_norm_bias))
+        self.optimizer = FusedAdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                    flat_order=model.parameters(), ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.scheduler = optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=num_epochs, eta_min=1e-5)
         # Data parallel (torch.distributed initialised, world > 1): every rank starts from rank 0's weights and the
         # gradients are summed over ranks in buckets as backward produces them (kdrt.ddp), for plain CE training as for KD.
         self.reducer = None
         if distributed():
             broadcast_module(model)
+            if ema_decay is not None:          # the EMA was cloned from this rank's own initial weights: restart it from rank 0's,
+                self.optimizer.reset_ema()     # so that it is the same function of the same parameters on every rank
             names = [n for n, p in model.named_parameters() if p.requires_grad]
             self.reducer = BucketedAllReduce(self.optimizer.flat, names, n_buckets=3)
         self.is_main = not distributed() or dist.get_rank() == 0
@@ -127,6 +161,13 @@ class Trainer:
         if max_grad_norm is not None:
             self.history.update({"grad_norm": [], "skipped_steps": []})
         self.last_epoch_grad_norm = None
+        # EMA on: validation, best.pth and the checkpoint's "ema_state" use the averaged weights (the model's own BatchNorm
+        # statistics with them); "val_miou_live" holds the live weights' mIoU when KD_EMA_VALIDATE_LIVE=1, None otherwise.
+        # The EMA is a function of the parameters, identical on every rank once it starts from the broadcast weights (above):
+        # no collective.
+        if ema_decay is not None:
+            self.history["val_miou_live"] = []
+        self.last_val_miou_live = None
 
     def _log(self, *a, **k):
         """Console output of the training loop: rank 0 only under data parallelism (errors and warnings of the other
@@ -179,6 +220,14 @@ class Trainer:
         return self._mean_over_ranks(total, len(self.train_loader)), metrics.compute()
 
     def validate(self):
+        if self.ema_decay is None:
+            return self._validate()
+        with self.optimizer.swap_ema():
+            out = self._validate()
+        self.last_val_miou_live = self._validate()[1]["miou"] if os.environ.get("KD_EMA_VALIDATE_LIVE") == "1" else None
+        return out
+
+    def _validate(self):
         self.model.eval()
         if distributed():
             broadcast_buffers(self.model)       # all ranks evaluate rank 0's BatchNorm statistics (the model that is saved)
@@ -199,6 +248,8 @@ class Trainer:
             return
         ckpt = {"epoch": epoch, "model_state": self.model.state_dict(), "optimizer_state": self.optimizer.state_dict(),
                 "scheduler_state": self.scheduler.state_dict(), "val_miou": val_miou}
+        if self.ema_decay is not None:         # loads with model.load_state_dict(ckpt["ema_state"]); "model_state" stays the live weights
+            ckpt["ema_state"] = self.optimizer.ema_state_dict(self.model)
         torch.save(ckpt, os.path.join(self.save_dir, "latest.pth"))
         if is_best:
             torch.save(ckpt, os.path.join(self.save_dir, "best.pth"))
@@ -207,6 +258,11 @@ class Trainer:
         ckpt = torch.load(path, map_location=self.device)
         self.model.load_state_dict(ckpt["model_state"])
         self.optimizer.load_state_dict(ckpt["optimizer_state"])
+        if self.ema_decay is not None:
+            if "ema_state" in ckpt:
+                self.optimizer.load_ema(ckpt["ema_state"], self.model)
+            else:                              # a checkpoint written without an EMA: the average starts from its weights
+                self.optimizer.reset_ema()
         if "scheduler_state" in ckpt:
             self.scheduler.load_state_dict(ckpt["scheduler_state"])
         self.best_miou = ckpt.get("val_miou", 0.0)
@@ -221,6 +277,8 @@ class Trainer:
         if self.max_grad_norm is not None:
             self.history["grad_norm"].append(self.last_epoch_grad_norm)
             self.history["skipped_steps"].append(self.optimizer.skipped_steps())
+        if self.ema_decay is not None:
+            self.history["val_miou_live"].append(self.last_val_miou_live)
         if self.is_main:                       # one writer: ranks share the working directory
             with open(self.history_path, "w") as f:
                 json.dump(self.history, f, indent=2)

@@ -2,7 +2,10 @@
 (3-class head, class weights [0.39, 2.61, 33.09], 30 epochs, interactive resume prompt:
 train_pandaset.py:79-163), on the MI355X-native path.  KD_DATA_ROOT overrides the dataset root.
 KD_LOADER_AUGMENT="rot=5,flip=0.5,jitter=0.02,..." turns the opt-in training augmentation on (training loader only;
-create_pandaset_dataloaders reads it, nothing changes here)."""
+create_pandaset_dataloaders reads it, nothing changes here).
+KD_EMA_DECAY=0.999 (with KD_EMA_WARMUP=1) validates and checkpoints an EMA of the weights, KD_NO_DECAY_NORM_BIAS=1 takes the weight
+decay off BatchNorm parameters and biases, KD_LR_MULT="camera_encoder=0.1,..." scales the learning rate per top-level module
+(src.training.trainer.optim_options_from_env); all unset: nothing changes."""
 import os
 
 import torch
@@ -11,7 +14,7 @@ from src.data_loading.pandaset_dataset import create_pandaset_dataloaders
 from src.models.camera_encoder import TwinLiteEncoder
 from src.models.fusion_module import CompleteSegmentationModel
 from src.models.lidar_encoder import LiDAREncoder
-from src.training.trainer import Trainer
+from src.training.trainer import Trainer, optim_options_from_env
 
 
 def main():
@@ -36,7 +39,8 @@ def main():
     save_dir = "checkpoints/pandaset_weighted"
     trainer = Trainer(model=model, train_loader=train_loader, val_loader=val_loader, device=device, lr=1e-3,
                       weight_decay=1e-3, save_dir=save_dir, class_weights=[0.39, 2.61, 33.09], num_epochs=30,
-                      max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None)
+                      max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None,
+                      **optim_options_from_env())
     start_epoch = 0
     ckpt_path = os.path.join(save_dir, "latest.pth")
     if os.path.exists(ckpt_path):

@@ -10,6 +10,11 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
   KD_HARD_LOSS   unset: the reference's weighted cross-entropy.  `focal_tversky`: focal + Tversky as the hard-label term
                  (kdrt.losses.RegionLoss), for CE and KD training alike; KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA
                  override its gamma (2), false-positive weight (0.7) and false-negative weight (0.3)
+  KD_EMA_DECAY   unset: off.  e.g. 0.999: keep an EMA of the weights inside the AdamW step; validation, best.pth and the
+                 checkpoint's "ema_state" use it.  KD_EMA_WARMUP=1: d_t = min(decay, (1 + t) / (10 + t)).
+                 KD_EMA_VALIDATE_LIVE=1 also validates the live weights (history "val_miou_live")
+  KD_NO_DECAY_NORM_BIAS   1: no weight decay on BatchNorm parameters and biases (every parameter with ndim <= 1)
+  KD_LR_MULT     "camera_encoder=0.1,...": learning-rate multiplier per top-level module of the model
 Launch with `python -m torch.distributed.run --nproc-per-node N` for data-parallel training: one process per GPU,
 frames sharded over ranks in equal counts (every rank runs the same number of steps), rank 0's initial weights
 broadcast, gradients all-reduced in buckets during backward (CE and KD training alike), BatchNorm statistics per
@@ -27,7 +32,7 @@ from src.data_loading.pandaset_dataset import create_pandaset_dataloaders
 from src.models.camera_encoder import TwinLiteEncoder
 from src.models.fusion_module import CompleteSegmentationModel
 from src.models.lidar_encoder import LiDAREncoder
-from src.training.trainer import KDTrainer, Trainer
+from src.training.trainer import KDTrainer, Trainer, optim_options_from_env
 
 _MAIN = [True]
 
@@ -75,6 +80,7 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
               class_weights=[0.4, 3.5], num_epochs=int(os.environ.get("KD_EPOCHS", 20)),
               max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None)
     kw["hard_loss"] = hard_loss_from_env()
+    kw.update(optim_options_from_env())        # KD_EMA_DECAY, KD_EMA_WARMUP, KD_NO_DECAY_NORM_BIAS, KD_LR_MULT: all unset = {}
     if kw["hard_loss"] is not None:
         log(f"  Hard-label loss: {kw['hard_loss']}")
     if teacher_ckpt:
