@@ -46,11 +46,18 @@ const char* kd_last_error_string(void);
  *          p0/p1/p2 = al/be/ga from kd_bn_bwd_finalize, p3/p4 = sc/sh of the mask or NULL)
  *   epi 0: store     epi 1: store + partial (sum, sum^2)      [forward, feeds kd_bn_finalize_train]
  *   epi 2: C *= act'(X*esc+esh); partial (sum C, sum C*xhat)  [dgrad, feeds kd_bn_bwd_finalize]
+ *   epi 5: C = epi_act((raw + bias)*esc + esh) (+ addend)      [inference: eval BatchNorm + activation in the epilogue]
+ *          pro 0 / 1 only; needs esc / esh [N] (16-byte aligned; kd_bn_eval_coeffs), no X, no partial.  Here the addend is
+ *          the block's residual and is added AFTER the activation (the bits of kd_bn_act_apply with `res`); with epi 0 / 1 / 2
+ *          it joins the raw result, before the bias, the statistics and the epi 2 mask.
  * The dgrad call passes W = transposed weight [K_out=Cin][N_red=Cout] (kd_transpose).
  * m_dev (optional device int): data-dependent row count <= M read by the kernel itself (no host sync). */
 /* Arithmetic of the GEMM family: 0 = exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = every fp32 operand split
  * exactly into three bf16 pieces and the six leading piece products accumulated in fp32 on the bf16 matrix pipe
- * (error <= 2^-23 |x||y| per product, i.e. fp32-grade).  Process-wide; returns the previous setting. */
+ * (fp32-grade: error <= 3.97 * 2^-24 |x||y| per product.  That is 1.5 x the worst single-product error measured on an MI355X,
+ * 2.65 * 2^-24 |x||y| over 1 M products per kernel form (tests/test_gpu_gemm_fp64.py); six sequentially nearest-rounded adds would
+ * give 1.67 * 2^-24, the matrix pipe's own accumulation rounds less tightly.  The exact-fp32 form meets 2^-24 |x||y|).
+ * Process-wide; returns the previous setting. */
 int kd_set_gemm_split(int on);
 int64_t kd_pwconv_stat_rows(int64_t M);
 int64_t kd_pwconv_stat_rows_for(int64_t M, int K, int N, int pro, int epi, int with_addend);

@@ -33,6 +33,9 @@ constexpr int BM = 128, BK = 32, LDSLD = 36;   // BM: slab-row granularity; 36-f
 // each an exact bf16 x bf16 product accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (32 cycles for K = 16
 // against 8 x 64 cycles of v_mfma_f32_32x32x2_f32): 6 x 32 = 192 cycles per 32x32x16 block instead of 512, so the
 // near-ridge shapes of this network (AI 14..64 FLOP/B) become HBM-bound instead of matrix-pipe-bound.
+// Per-product error: <= 3.97 * 2^-24 |x||y| -- 1.5 x the worst 2.65 * 2^-24 |x||y| measured on an MI355X over 1 M single products per
+// kernel form (tests/test_gpu_gemm_fp64.py: one non-zero per reduction).  Six sequentially nearest-rounded fp32 adds, smallest first,
+// would give 1.67 * 2^-24 (largest first: 4.7); the instruction's own accumulation rounds less tightly than that emulation.
 // (LDS image of the split operands: see SPROW below.)
 // Split LDS image: [plane][row][32 bf16], rows of exactly 64 bytes, no padding, with the four 16-byte chunks of a
 // row XOR-swizzled by (row >> 2) & 3.  ds_read_b128 is served in lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (and

@@ -148,8 +148,9 @@ def bn_eval_coeffs(bn, bnc: BNC):
 
 def set_gemm_arithmetic(mode: str) -> str:
     """'fp32': exact-fp32 MFMA products (v_mfma_f32_32x32x2_f32); 'split': every fp32 operand cut exactly into three
-    bf16 pieces, six leading piece products accumulated in fp32 on the bf16 matrix pipe (fp32-grade: <= 2^-23 |x||y|
-    per product).  Process-wide; returns the previous mode."""
+    bf16 pieces, six leading piece products accumulated in fp32 on the bf16 matrix pipe (fp32-grade: <= 3.97 * 2^-24 |x||y|
+    per product, 1.5 x the worst 2.65 * 2^-24 |x||y| measured on an MI355X by tests/test_gpu_gemm_fp64.py).  Process-wide;
+    returns the previous mode."""
     if mode not in ("fp32", "split"):
         raise KDError(f"unknown GEMM arithmetic {mode!r} (expected 'fp32' or 'split')")
     return "split" if lib.kd_set_gemm_split(1 if mode == "split" else 0) else "fp32"
