@@ -90,6 +90,21 @@ int kd_pwconv_wgrad(const float* D, int64_t ldd, const float* X, int64_t ldx, in
                     const float* al, const float* be, const float* ga, const float* msc, const float* msh,
                     const float* A, int64_t lda, int a_mode, int a_act, const float* asc, const float* ash,
                     float* dW, int64_t M, int N, int K, void* ws, size_t ws_bytes, void* stream);
+/* Data gradient and weight gradient of one 1x1 layer in ONE launch (csrc/kd_wgrad_rs.hip): the role-specialised weight-gradient
+ * kernel with the data gradient dX[M,K] = Deff[M,N] . Wt[K,N]^T on a matrix wave that plan leaves idle, from the D planes already
+ * in LDS -- D and X are read and converted once instead of twice.  One instance: N = 192, K = 32 (the stage-2 expand layer),
+ * split arithmetic, d_mode 0 / 2, a_mode 0, epi 0, no addend, kd_set_wgrad_rs != 0; kd_pwconv_bwd_supported answers 0 for everything
+ * else and the caller keeps kd_pwconv_wgrad + kd_pwconv_gemm.  dW has the bits of kd_pwconv_wgrad (default mode), dX those of
+ * kd_pwconv_gemm(pro = d_mode, epi 0) with W = Wt.  D, X, A, dX dense (ldd == ldx == N, lda == lddx == K);
+ * ws >= kd_pwconv_bwd_ws_bytes (the weight-gradient slab + a 256-byte line that absorbs the stores of rows beyond M).
+ * Any unsupported call is refused with a status < 0 and no launch. */
+int kd_pwconv_bwd_supported(int N, int K, int d_mode, int a_mode, int epi);
+size_t kd_pwconv_bwd_ws_bytes(int64_t M, int N, int K);
+int kd_pwconv_bwd(const float* D, int64_t ldd, const float* X, int64_t ldx, int d_mode, int d_act,
+                  const float* al, const float* be, const float* ga, const float* msc, const float* msh,
+                  const float* A, int64_t lda, int a_mode, int a_act, const float* asc, const float* ash,
+                  const float* Wt, float* dX, int64_t lddx, const float* addend, int64_t ldadd, int epi,
+                  float* dW, int64_t M, int N, int K, void* ws, size_t ws_bytes, void* stream);
 int kd_transpose(const float* in, float* out, int R, int C, void* stream);
 /* the same for n weights in one launch: table = device int64 [n][5] {in pointer, out pointer, R, C, first 256-element block of
  * this matrix}, first blocks ascending from 0, nblocks = sum of ceil(R*C/256) */

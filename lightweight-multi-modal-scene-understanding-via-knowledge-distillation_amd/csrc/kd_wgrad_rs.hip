@@ -44,9 +44,18 @@ struct RsGeom {               // runtime part of the configuration (the template
   int rows_per_slice;         // multiple of the chunk height
 };
 
+// The data-gradient role (DG != 0): dX[M,K] = Deff[M,N] . Wt[K,N]^T from the D planes the weight gradient already has in LDS
+struct RsDgrad {
+  const float* Wt;            // [K][N] row-major (the weight, transposed by the caller: the W operand of the dgrad pw_gemm)
+  float* dX;                  // [M][K] dense
+  float* dump;                // [64] floats of workspace that absorb the stores of rows beyond the slice's end
+};
+
 // TNW x TKW: 32x32 accumulator tiles per matrix wave; NBLK = TNW * WN, KBLK = TKW * WK; CHK: 16-row steps per chunk
-template <int TNW, int TKW, int WNc, int WKc, int CHK, int DMODE, int AMODE>
-__global__ __launch_bounds__(RS_THREADS, 1) void pw_wgrad_rs_kernel(WgradArgs g, RsGeom q) {
+// DG: 0 weight gradient only; 1 / 2 (192 x 32 plan only): matrix wave 6, idle in that plan, also computes the data gradient
+// (2: dX is stored with the non-temporal hint)
+template <int TNW, int TKW, int WNc, int WKc, int CHK, int DMODE, int AMODE, int DG>
+__global__ __launch_bounds__(RS_THREADS, 1) void pw_wgrad_rs_kernel(WgradArgs g, RsGeom q, RsDgrad dg) {
   constexpr int NBLK = TNW * WNc, KBLK = TKW * WKc;
   constexpr int CH = 16 * CHK;                                   // rows per chunk
   constexpr int PD = rs_pitch(NBLK), PA = rs_pitch(KBLK);        // bf16 per LDS row
@@ -72,6 +81,81 @@ __global__ __launch_bounds__(RS_THREADS, 1) void pw_wgrad_rs_kernel(WgradArgs g,
   if (mend > g.M) mend = g.M;
   const int nchunk = mbeg < mend ? (int)((mend - mbeg + CH - 1) / CH) : 0;
   const int nstep = (nchunk + 1) & ~1;                           // both roles run an even number of steps (two register sets)
+
+  if constexpr (DG != 0) {
+    // ================= data-gradient wave =================
+    // The 192 x 32 plan keeps two of the four matrix waves busy; wave 6 takes every chunk's dX[32,32] = Deff[32,192] . Wt^T.
+    // Arithmetic of pw_gemm_kernel<2, 0, 4, 1, SPLIT> (kd_gemm.hip), bit for bit: the A operand is the row fragment of the D
+    // planes (row lane & 31, eight consecutive n at 16 ks + 8 (lane >> 5)) -- the very bf16 pieces that kernel's prologue makes
+    // of the same fp32 values --, the B operand the same fragment of Wt; k-steps 0..11 in order into ONE accumulator, six
+    // products per step in the PAo / PBo order.  A block is never shared between waves and 16x16 MFMAs are not used: either
+    // would change the summation order.
+    //   Weight planes: 12 k-steps x 3 pieces x 4 registers = 144 VGPRs, split once per launch (the 120 KB plane image leaves
+    // no LDS for them; lidar_l2_bwd_kernel keeps 96 the same way).
+    //   LDS reads: 36 ds_read_b128 per chunk over rows of 448 bytes.  448 B = 112 banks = 48 mod 64, so rows r and r + 4 start
+    // in the same bank and the 32 rows of a fragment fall into only 16 of the 64 banks: each 16-lane group of the read
+    // ({0-3, 12-15, 20-27}, ...) holds four rows per bank quartet -- a 4-way conflict, 16 LDS cycles per read instead of 4,
+    // 36 x 16 = 576 cycles (~0.25 us) per chunk next to the ~900 cycles of the other roles' plane stores and transposing reads
+    // and the ~3 us a chunk takes (HBM-bound).  No permutation of rows among lanes helps (all 32 rows of one column group
+    // live in those 16 banks) and a swizzle of the column groups would have to serve the 8-byte plane stores and the
+    // transposing reads of the weight gradient as well; at a tenth of the chunk time the conflict is accepted.
+    //   72 MFMAs in one chain = 72 x 32 cycles = 2304 cycles (~1 us) per chunk on a SIMD whose matrix pipe was idle.
+    //   Stores: straight from the accumulator, no LDS stage: a dX row is one 128-byte segment and a store instruction writes
+    // two of them (lanes 0-31 row i, lanes 32-63 row i + 4).  Rows beyond the slice's end (and the padding step) go to a dump
+    // line by a pointer select: no branch between memory operations, as in the other roles.  The stores come AFTER the step's
+    // barrier (which needs the plane reads only): waiting for the last MFMA and issuing 16 stores in front of it held the other
+    // seven waves up (measured at 256 frames: x1.57 -> x1.65 against the two launches).
+    //   Measured at 256 frames (tools/bench_pw_bwd.py, profiles/pw_bwd_fused_ab.txt): 1.56 ms against 1.27 + 1.21 ms for the two
+    // launches; 233 VGPRs, no scratch, one workgroup per CU.
+    static_assert(TNW == 3 && TKW == 1 && WNc == 2 && WKc == 1 && CHK == 2 && AMODE == 0, "the data-gradient role exists for the 192 x 32 plan only");
+    if (wave == 6) {
+      constexpr int KSN = 2 * NBLK;                                // 16-wide k-steps of the reduction over N
+      constexpr int PAo[6] = {0, 2, 1, 0, 1, 0}, PBo[6] = {2, 0, 1, 1, 0, 0};
+      const int r = lane & 31, h = lane >> 5;
+      bf16x8 wp[KSN][3];
+      {
+        const float* wrow = dg.Wt + r * (32 * NBLK) + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+          uint2 h0, m0_, l0, h1, m1_, l1;
+          kd_split3(kd_ld4(wrow + 16 * ks), h0, m0_, l0);
+          kd_split3(kd_ld4(wrow + 16 * ks + 4), h1, m1_, l1);
+          wp[ks][0] = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
+          wp[ks][1] = __builtin_bit_cast(bf16x8, make_uint4(m0_.x, m0_.y, m1_.x, m1_.y));
+          wp[ks][2] = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
+        }
+      }
+      const int foff = r * PD + 8 * h;                             // the lane's fragment inside a plane
+      const int ooff = 4 * h * (32 * KBLK) + r;                    // ... and its first output element inside a chunk of dX
+      float* const dlane = dg.dump + lane;
+      kd_lds_barrier();                                            // (the prologue's)
+      for (int s = 0; s < nstep; ++s) {
+        const unsigned short* bd = lds + (s & 1) * BUF + foff;
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < KSN; ++ks) {
+          bf16x8 a[3];
+#pragma unroll
+          for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(bd + p * PLD + 16 * ks);
+#pragma unroll
+          for (int t = 0; t < 6; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PAo[t]], wp[ks][PBo[t]], acc, 0, 0, 0);
+        }
+        kd_lds_barrier();                                          // the plane reads are done; the stores are not on the barrier's path
+        const int64_t m0 = mbeg + (int64_t)s * CH;
+        const int left = s < nchunk ? (int)(mend - m0) : 0;        // rows of this chunk inside the slice
+        float* const ob = dg.dX + m0 * (32 * KBLK) + ooff;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int row = (i & 3) + 8 * (i >> 2);                  // (+ 4 h: in ooff)
+          float* const dst = row + 4 * h < left ? ob + row * (32 * KBLK) : dlane;
+          if (DG == 2) __builtin_nontemporal_store(acc[i], dst); else *dst = acc[i];
+        }
+      }
+      return;
+    }
+  }
 
   if (wave < 4) {
     // ================= vector waves =================
@@ -292,9 +376,9 @@ int rs_launch_shape(const WgradArgs& g, const RsGeom& q, hipStream_t st) {
 #define KD_RS_CASE(DM_, AM_)                                                                                              \
   if (g.d_mode == DM_ && g.a_mode == AM_) {                                                                               \
     static std::atomic<uint64_t> raised{0};                                                                               \
-    const hipError_t e = kd_raise_dynamic_lds((const void*)pw_wgrad_rs_kernel<TNW, TKW, WN, WK, CHK, DM_, AM_>, lds, raised); \
+    const hipError_t e = kd_raise_dynamic_lds((const void*)pw_wgrad_rs_kernel<TNW, TKW, WN, WK, CHK, DM_, AM_, 0>, lds, raised); \
     if (e != hipSuccess) { kd_set_error("kd_wgrad_rs: cannot raise the dynamic LDS limit to %zu B: %s", lds, hipGetErrorString(e)); return -1; } \
-    hipLaunchKernelGGL((pw_wgrad_rs_kernel<TNW, TKW, WN, WK, CHK, DM_, AM_>), grid, blk, lds, st, g, q);                  \
+    hipLaunchKernelGGL((pw_wgrad_rs_kernel<TNW, TKW, WN, WK, CHK, DM_, AM_, 0>), grid, blk, lds, st, g, q, RsDgrad{});    \
     return 1;                                                                                                             \
   }
   KD_RS_CASE(0, 0) KD_RS_CASE(0, 1) KD_RS_CASE(2, 0) KD_RS_CASE(2, 1)
@@ -312,6 +396,20 @@ int rs_slices(int64_t M, const RsPlan& p) {
   return nrs < 1 ? 1 : nrs;
 }
 
+// geometry of a launch over nrs0 row slices (rs_slices, or fewer where the workspace is smaller): whole chunks per slice
+RsGeom rs_geom(int64_t M, const RsPlan& p, int nrs0) {
+  const int ch = 16 * p.chk;
+  const int64_t chunks = (M + ch - 1) / ch;
+  const int64_t cps = (chunks + nrs0 - 1) / nrs0;
+  RsGeom q{p.wn, p.wk, p.ncs, p.split_n, 0, (int)(cps * ch)};
+  q.nrs = (int)((M + q.rows_per_slice - 1) / q.rows_per_slice);
+  return q;
+}
+
+constexpr int BWD_N = 192, BWD_K = 32, BWD_DUMP = 64;            // the one layer shape of the data + weight gradient form; floats of its dump line
+
+bool bwd_plan(RsPlan& p) { return rs_plan(BWD_N, BWD_K, p) && p.tnw == 3 && p.tkw == 1 && p.wn == 2 && p.wk == 1 && p.chk == 2 && p.ncs == 1; }
+
 }  // namespace
 
 extern "C" int kd_set_wgrad_rs(int mode) { return g_rs_on.exchange(mode < 0 ? 0 : (mode > 2 ? 2 : mode)); }
@@ -328,15 +426,11 @@ int kd_wgrad_rs_launch(const WgradArgs& g0, size_t ws_bytes, float* dW, hipStrea
   RsPlan p;
   if (!rs_enabled() || !kd_gemm_split_mode() || (g0.d_mode != 0 && g0.d_mode != 2) || g0.a_mode > 1 || !rs_plan(g0.N, g0.K, p)) return 0;
   WgradArgs g = g0;
-  const int ch = 16 * p.chk;
   int nrs = rs_slices(g.M, p);
   const size_t cap = ws_bytes / ((size_t)g.N * g.K * sizeof(float));
   if ((size_t)nrs > cap) nrs = (int)cap;
   if (nrs < 1) return 0;
-  const int64_t chunks = ((int64_t)g.M + ch - 1) / ch;
-  const int64_t cps = (chunks + nrs - 1) / nrs;
-  RsGeom q{p.wn, p.wk, p.ncs, p.split_n, 0, (int)(cps * ch)};
-  q.nrs = (int)(((int64_t)g.M + q.rows_per_slice - 1) / q.rows_per_slice);
+  const RsGeom q = rs_geom(g.M, p, nrs);
   int rc = 0;
 #define KD_RS_SHAPE(A_, B_, C_, D_, E_) if (p.tnw == A_ && p.tkw == B_ && p.wn == C_ && p.wk == D_ && p.chk == E_) rc = rs_launch_shape<A_, B_, C_, D_, E_>(g, q, st);
   KD_RS_SHAPE(3, 1, 2, 1, 2) KD_RS_SHAPE(3, 2, 4, 1, 1) KD_RS_SHAPE(2, 4, 4, 1, 1) KD_RS_SHAPE(1, 3, 2, 2, 2) KD_RS_SHAPE(1, 12, 4, 1, 1)
@@ -347,3 +441,76 @@ int kd_wgrad_rs_launch(const WgradArgs& g0, size_t ws_bytes, float* dW, hipStrea
   if (e) return -1;
   return kd_slab_reduce_launch(g.slab, q.nrs, (int64_t)g.N * g.K, dW, st) == KD_OK ? 1 : -1;
 }
+
+
+// ---- stage-2 expand backward: data gradient + weight gradient in one launch -------------------------------------------------
+// unit_backward used to launch pw_wgrad_rs_kernel and then the data-gradient pw_gemm_kernel for every 1x1 layer; both read and
+// convert the same (dY, Y).  For the 192 x 32 layer -- the largest such pair of the step, and the plan with idle matrix waves --
+// kd_pwconv_bwd runs both in the weight-gradient kernel (DG != 0 above): 7.5 GB of HBM traffic instead of 14.5 GB at 256 frames.
+// dW: the slab order of kd_wgrad_rs_launch (rs_slices, rs_geom), so the bits of kd_pwconv_wgrad in its default mode;
+// dX: the bits of kd_pwconv_gemm(pro 2 / 0, epi 0).
+extern "C" {
+
+int kd_pwconv_bwd_supported(int N, int K, int d_mode, int a_mode, int epi) {
+  RsPlan p;
+  return N == BWD_N && K == BWD_K && (d_mode == 0 || d_mode == 2) && a_mode == 0 && epi == 0 && kd_gemm_split_mode() && rs_enabled() && bwd_plan(p);
+}
+
+size_t kd_pwconv_bwd_ws_bytes(int64_t M, int N, int K) {
+  RsPlan p;
+  if (N != BWD_N || K != BWD_K || M < 1 || !bwd_plan(p)) return 0;
+  return ((size_t)rs_slices(M, p) * (size_t)N * (size_t)K + BWD_DUMP) * sizeof(float);
+}
+
+// The arguments of kd_pwconv_wgrad plus the data gradient's: Wt [K][N] (the weight transposed, as kd_pwconv_gemm takes it),
+// dX [M][K], the epilogue id of that GEMM (only 0 has an instance) and its optional addend (refused: no instance).
+int kd_pwconv_bwd(const float* D, int64_t ldd, const float* X, int64_t ldx, int d_mode, int d_act, const float* al,
+                  const float* be, const float* ga, const float* msc, const float* msh, const float* A, int64_t lda,
+                  int a_mode, int a_act, const float* asc, const float* ash, const float* Wt, float* dX, int64_t lddx,
+                  const float* addend, int64_t ldadd, int epi, float* dW, int64_t M, int N, int K, void* ws, size_t ws_bytes,
+                  void* stream) {
+  KD_REQUIRE(D && A && Wt && dX && dW && ws && M > 0 && N > 0 && K > 0, KD_ERR_ARG, "kd_pwconv_bwd: null pointer or empty shape");
+  KD_REQUIRE(kd_pwconv_bwd_supported(N, K, d_mode, a_mode, epi), KD_ERR_SHAPE,
+             "kd_pwconv_bwd: no instance for N=%d K=%d d_mode=%d a_mode=%d epi=%d in the %s arithmetic%s (use kd_pwconv_wgrad + kd_pwconv_gemm)",
+             N, K, d_mode, a_mode, epi, kd_gemm_split_mode() ? "split" : "exact-fp32", rs_enabled() ? "" : " with kd_set_wgrad_rs(0)");
+  KD_REQUIRE(!addend, KD_ERR_ARG, "kd_pwconv_bwd: no instance with an addend (ldadd=%lld) (use kd_pwconv_wgrad + kd_pwconv_gemm)", (long long)ldadd);
+  KD_REQUIRE(M < (int64_t)1 << 31, KD_ERR_SHAPE, "kd_pwconv_bwd: M too large");
+  KD_REQUIRE(ldd == N && (d_mode != 2 || ldx == N) && lda == K && lddx == K, KD_ERR_SHAPE,
+             "kd_pwconv_bwd: D, X, A and dX must be dense matrices (row strides %lld, %lld, %lld, %lld)", (long long)ldd, (long long)ldx,
+             (long long)lda, (long long)lddx);
+  if (d_mode == 2) KD_REQUIRE(X && al && be && ga, KD_ERR_ARG, "kd_pwconv_bwd: d_mode 2 needs X, al, be, ga");
+  if (d_mode == 2 && d_act != KD_ACT_NONE) KD_REQUIRE(msc && msh, KD_ERR_ARG, "kd_pwconv_bwd: mask needs sc/sh");
+  KD_REQUIRE(kd_aligned16(D) && kd_aligned16(X) && kd_aligned16(A) && kd_aligned16(Wt) && kd_aligned16(dX) && kd_aligned16(ws) &&
+             kd_aligned16(al) && kd_aligned16(be) && kd_aligned16(ga) && kd_aligned16(msc) && kd_aligned16(msh), KD_ERR_ALIGN,
+             "kd_pwconv_bwd: 16-byte alignment");
+  KD_REQUIRE(ws_bytes >= kd_pwconv_bwd_ws_bytes(M, N, K), KD_ERR_WORKSPACE, "kd_pwconv_bwd: workspace too small (%zu B)", ws_bytes);
+  if (d_mode == 2 && !msc) { msc = al; msh = al; }       // mask disabled (act none): any valid vector will do
+  RsPlan p;
+  bwd_plan(p);
+  const int nrs0 = rs_slices(M, p);
+  const RsGeom q = rs_geom(M, p, nrs0);
+  float* slab = (float*)ws;
+  WgradArgs g{D, ldd, X, ldx, al, be, ga, msc, msh, d_mode, d_act, A, lda, asc, ash, a_mode, a_act, slab, (int)M, N, K, 0, nullptr, nullptr};
+  const RsDgrad dgr{Wt, dX, slab + (size_t)nrs0 * N * K};
+  const int nt = kd_nt_store((size_t)M * K * sizeof(float));
+  constexpr size_t lds = (size_t)2 * 3 * 32 * (rs_pitch(6) + rs_pitch(1)) * 2;
+  const dim3 grid((unsigned)q.nrs), blk(RS_THREADS);
+  hipStream_t st = (hipStream_t)stream;
+  bool launched = false;
+#define KD_BWD_CASE(DM_, DG_)                                                                                             \
+  if (d_mode == DM_ && nt + 1 == DG_) {                                                                                   \
+    static std::atomic<uint64_t> raised{0};                                                                               \
+    const hipError_t e = kd_raise_dynamic_lds((const void*)pw_wgrad_rs_kernel<3, 1, 2, 1, 2, DM_, 0, DG_>, lds, raised);  \
+    KD_REQUIRE(e == hipSuccess, (int)e, "kd_pwconv_bwd: cannot raise the dynamic LDS limit to %zu B: %s", lds, hipGetErrorString(e)); \
+    hipLaunchKernelGGL((pw_wgrad_rs_kernel<3, 1, 2, 1, 2, DM_, 0, DG_>), grid, blk, lds, st, g, q, dgr);                  \
+    launched = true;                                                                                                      \
+  }
+  KD_BWD_CASE(0, 1) KD_BWD_CASE(0, 2) KD_BWD_CASE(2, 1) KD_BWD_CASE(2, 2)
+#undef KD_BWD_CASE
+  KD_REQUIRE(launched, KD_ERR_ARG, "kd_pwconv_bwd: no kernel for d_mode=%d", d_mode);
+  const int rc = kd_check_launch("kd_pwconv_bwd");
+  if (rc) return rc;
+  return kd_slab_reduce_launch(slab, q.nrs, (int64_t)N * K, dW, st);
+}
+
+}  // extern "C"

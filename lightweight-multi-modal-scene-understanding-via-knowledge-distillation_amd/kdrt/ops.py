@@ -334,6 +334,22 @@ def pw_wgrad(D, A, dW, *, M, N, K, X=None, d_mode=0, d_act=0, al=None, be=None, 
     _prof_end(e0, "pw_wgrad", 2.0 * M * N * K, 4.0 * (M * N * (2 if d_mode == 2 else 1) + M * K + N * K), None, M)
 
 
+def pw_bwd(D, A, Wt, dX, dW, *, M, N, K, X=None, d_mode=0, d_act=0, al=None, be=None, ga=None, msc=None, msh=None,
+           a_mode=0, a_act=0, asc=None, ash=None, addend=None, epi=0):
+    """Data gradient dX = Deff . Wt^T and weight gradient dW = Deff^T . A of a 1x1 layer in ONE launch (csrc/kd_wgrad_rs.hip):
+    pw_wgrad + pw_gemm(pro 2, epi 0) with D and X read and converted once.  The library refuses every combination
+    kd_pwconv_bwd_supported does not name (the caller then keeps the two kernels)."""
+    nbytes = lib.kd_pwconv_bwd_ws_bytes(M, N, K)
+    ws = workspace(nbytes, D.device)
+    e0 = _prof_begin()
+    lib.call("kd_pwconv_bwd", P(D), ld(D), P(X), ld(X) if X is not None else 0, d_mode, d_act, P(al), P(be), P(ga),
+             P(msc), P(msh), P(A), ld(A), a_mode, a_act, P(asc), P(ash), P(Wt), P(dX), ld(dX), P(addend),
+             ld(addend) if addend is not None else 0, epi, P(dW), M, N, K, P(ws), nbytes, stream())
+    # both GEMMs' FLOPs; algorithmic traffic of THIS launch: D (and X) and A in, dX out, the weight in and its gradient out
+    _prof_end(e0, "pw_bwd", 4.0 * M * N * K,
+              4.0 * (M * N * (2 if d_mode == 2 else 1) + 2 * M * K + (addend is not None) * M * K + 2 * N * K), None, M)
+
+
 class TransposeCache:
     """W^T of every weight the data-gradient GEMMs need, refreshed by ONE launch per step instead of one per weight.
 

@@ -380,7 +380,12 @@ def unit_backward(rec: _Rec, g, need_input_grad: bool = True, addend: Optional[t
                  and ld(y) == N and ld(inp.raw) == K)               # (dense operands: the one-kernel form addresses rows by 128)
         fused1 = (inp.virt is not None and need_input_grad and addend is None and not tables
                   and mact == ACT_NONE and inp.act == ACT_RELU and lib.kd_lidar_l1_bwd_supported(N, K) and ld(t) == N and ld(y) == N)
-        if fused or fused1:
+        # a materialised input whose layer shape has the one-launch form (csrc/kd_wgrad_rs.hip: the stage-2 expand layer): dX and dW
+        # from one read of (t, y); same bits as the two launches
+        a_mode = 1 if inp.bnc is not None else 0
+        fused_pw = (_PW_BWD_FUSED and need_input_grad and not tables and inp.virt is None and inp.bnc is None and addend is None
+                    and lib.kd_pwconv_bwd_supported(N, K, 2, a_mode, 0) and ld(t) == N and ld(y) == N and ld(inp.raw) == K)
+        if fused or fused1 or fused_pw:
             pass            # data gradient and weight gradient in one kernel, below
         elif tables:
             ops.l2_wgrad(t, out_op, dW, inp=inp, al=al, be=be, ga=ga)
@@ -388,10 +393,15 @@ def unit_backward(rec: _Rec, g, need_input_grad: bool = True, addend: Optional[t
             ops.l1_wgrad(t, y, dW, op=inp, al=al, be=be, ga=ga, msc=msc, msh=msh, mact=mact)
         else:
             ops.pw_wgrad(t, inp.raw, dW, M=M, N=N, K=K, X=y, d_mode=2, d_act=mact, al=al, be=be, ga=ga, msc=msc, msh=msh,
-                         a_mode=1 if inp.bnc is not None else 0, a_act=inp.act, asc=inp.sc, ash=inp.sh)
+                         a_mode=a_mode, a_act=inp.act, asc=inp.sc, ash=inp.sh)
         if need_input_grad:
             Wt = ops.transpose(rec.w.view(N, K), owner=rec.w)
-            if fused1:
+            if fused_pw:
+                dx = torch.empty(M, K, device=dev, dtype=torch.float32)
+                ops.pw_bwd(t, inp.raw, Wt, dx, dW, M=M, N=N, K=K, X=y, d_mode=2, d_act=mact, al=al, be=be, ga=ga, msc=msc, msh=msh,
+                           a_mode=0, a_act=inp.act)
+                g_in = dx
+            elif fused1:
                 rows_in = lib.kd_lidar_l1_bwd_stat_rows(M)
                 part_in = torch.empty(rows_in * 2 * K, device=dev, dtype=torch.float32)
                 m1 = torch.empty(4, K, device=dev, dtype=torch.float32)
@@ -1077,6 +1087,9 @@ _SCATTER_TABLES = True
 _SCATTER_HOLDERS = True
 # the whole eval-mode encoder (point MLP + scatter-max) in one kernel (csrc/kd_lidar_infer.hip); False: layer by layer
 _LIDAR_FUSED_INFER = True
+# the data gradient and the weight gradient of a 1x1 layer with a materialised input in one launch where the library has an
+# instance (kd_pwconv_bwd_supported: the stage-2 expand layer); False: kd_pwconv_wgrad + kd_pwconv_gemm (A/B, tests; same bits)
+_PW_BWD_FUSED = True
 
 
 _sort_cache: dict = {}
