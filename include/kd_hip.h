@@ -562,6 +562,18 @@ int kd_adamw_step_groups_dev(float* p, const float* g, float* m, float* v, int64
                              const float* group_state, int n_groups, float* ema, float* ema_state, float ema_decay, int ema_warmup,
                              float* clip_state, void* ws, size_t ws_bytes, float beta1, float beta2, float eps, float ginv,
                              float max_norm, void* stream);
+/* Gradient accumulation over micro-batches: the backward kernels overwrite the flat gradient buffer, the running sum lives in
+ * `accum`, a second buffer of the same length.
+ *   fold 0: accum[i] = accum[i] + grad[i]; grad is only read                       (micro-batches 1 .. k-1 of a cycle)
+ *   fold 1: grad[i] = accum[i] + grad[i] and accum[i] = +0.0f in the same pass     (micro-batch k: the AdamW entry points above
+ *           then step on the summed gradient with ginv / k, and the next cycle -- or the next replay of a captured graph --
+ *           starts from zeros without a memset)
+ * One fp32 add per element with accum as the left operand: the bits of torch's `accum + grad`.  One launch: 256 threads, one
+ * float4 per thread and iteration, at most 2048 blocks, the last n % 4 elements one by one; any n >= 0, n == 0 returns 0 without
+ * a launch.  accum == grad, a null pointer with n > 0, n < 0 or fold outside {0, 1}: KD_ERR_ARG; accum and grad 16-byte aligned
+ * (KD_ERR_ALIGN; every tensor, and so every gradient bucket, of kdrt.optim.FlatParams starts on such a boundary).  A refused call
+ * launches nothing. */
+int kd_grad_accumulate(float* accum, float* grad, int64_t n, int fold, void* stream);
 
 /* ---- inference-mode block fusion (csrc/kd_block.hip) ------------------------------------------------------------------
  * The tail of an InvertedResidual (reference camera_encoder.py:30-42: depthwise 3x3 + BN + ReLU6, project 1x1 + BN, + x) or a

@@ -640,3 +640,59 @@ int kd_adamw_step_groups_dev(float* p, const float* g, float* m, float* v, int64
 }
 
 }  // extern "C"
+
+// ---- gradient accumulation over micro-batches ------------------------------------------------------------------------------
+// Backward kernels overwrite their slot of the flat gradient buffer, so the sum over k micro-batches lives in a second flat
+// buffer.  FOLD = false: accum += grad (micro-batches 1 .. k-1).  FOLD = true: grad = accum + grad and accum = +0 in the same
+// pass (micro-batch k: the optimiser step then reads the sum where it reads the gradient today, and the next cycle -- or the
+// next replay of a captured graph -- starts from zeros without a memset).  One fp32 add per element, accum the left operand:
+// nothing to contract, the bits of torch's `accum + grad`.
+namespace {
+
+constexpr int GACC_CAP = 2048;
+
+template <bool FOLD>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* accum, float* grad, int64_t n) {
+  const int64_t n4 = n / 4;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 a = kd_ld4(accum + i * 4), g = kd_ld4(grad + i * 4);
+    const float4 s = make_float4(a.x + g.x, a.y + g.y, a.z + g.z, a.w + g.w);
+    if (FOLD) {
+      kd_st4(grad + i * 4, s);
+      kd_st4(accum + i * 4, kd_zero4());
+    } else {
+      kd_st4(accum + i * 4, s);
+    }
+  }
+  const int64_t t = n4 * 4 + threadIdx.x;          // the scalar tail: at most three elements, block 0
+  if (blockIdx.x == 0 && t < n) {
+    const float s = accum[t] + grad[t];
+    if (FOLD) {
+      grad[t] = s;
+      accum[t] = 0.f;
+    } else {
+      accum[t] = s;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int kd_grad_accumulate(float* accum, float* grad, int64_t n, int fold, void* stream) {
+  KD_REQUIRE(n >= 0 && (fold == 0 || fold == 1), KD_ERR_ARG, "kd_grad_accumulate: bad args (n = %lld, fold = %d)", (long long)n, fold);
+  if (n == 0) return KD_OK;
+  KD_REQUIRE(accum && grad && accum != grad, KD_ERR_ARG, "kd_grad_accumulate: accum and grad must be two non-null buffers");
+  KD_REQUIRE(kd_aligned16(accum) && kd_aligned16(grad), KD_ERR_ALIGN, "kd_grad_accumulate: accum and grad must be 16-byte aligned");
+  int64_t grid = (n / 4 + 255) / 256;
+  if (grid > GACC_CAP) grid = GACC_CAP;
+  if (grid < 1) grid = 1;
+  if (fold)
+    hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, accum, grad, n);
+  else
+    hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, accum, grad, n);
+  return kd_check_launch("kd_grad_accumulate");
+}
+
+}  // extern "C"

@@ -50,11 +50,18 @@ class BucketedAllReduce:
     identity, so the step must stay bit-identical to the reducer-less step -- which is how the whole RCCL path
     (communicator, ProcessGroupNCCL's side stream and events, async work handles, `wait()` ordering before AdamW) is
     executed and checked on a 1-GPU box (tests/test_gpu_rccl_world1.py, `bench.py --force-reducer`).
-    `enabled=False` silences the hooks (a second, reducer-less KDStep over the same parameters)."""
+    `enabled=False` silences the hooks (a second, reducer-less KDStep over the same parameters).
+
+    Gradient accumulation (optim.AccumCycle, k micro-batches per optimiser step): the owner keeps `enabled` False on the first
+    k-1 micro-batches of a cycle -- no hook fires, no `finish()` is called, no collective is issued -- and True on the last.
+    `fold(lo, hi)` (FusedAdamW.fold, set by the owner; None without accumulation) is then called on a bucket's slice of the flat
+    buffer, in floats, right before that bucket is reduced: the bucket's gradients become the sum over the cycle the moment its
+    last gradient of the last micro-batch lands, and the reduction still overlaps the rest of backward."""
 
     def __init__(self, flat: FlatParams, names: Optional[Sequence[str]] = None, n_buckets: int = 3, group=None,
-                 force: Optional[bool] = None):
+                 force: Optional[bool] = None, fold=None):
         self.flat, self.group = flat, group
+        self.fold = fold
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.force = (os.environ.get("KD_FORCE_REDUCER") == "1") if force is None else bool(force)
         if self.force and not dist.is_initialized():
@@ -119,6 +126,9 @@ class BucketedAllReduce:
 
     def _launch(self, b):
         self.launch_order.append(b)
+        if self.fold is not None:          # before the early return too: a world of one rank still has to fold
+            a, e = self.spans[b]
+            self.fold(self.flat.offsets[a], self.flat.offsets[e])
         if self.world == 1 and not self.force:
             return
         # Canonical async collective: ProcessGroupNCCL (RCCL) runs it on its own internal stream, ordered

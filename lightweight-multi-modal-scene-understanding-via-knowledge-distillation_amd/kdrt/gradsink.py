@@ -3,7 +3,10 @@ flat gradient buffer instead of returning fresh tensors for autograd to `+=` int
 (96 tiny add kernels + copies per step otherwise).
 
 Contract while a sink is installed: every registered parameter receives at most ONE gradient per
-step (no weight sharing, no multi-backward accumulation) -- a second write in the same step raises.
+micro-batch, i.e. between two begin_step() calls (no weight sharing, no second backward pass over
+the same buffer) -- a second write raises.  The kernels overwrite their slot, so gradient
+accumulation over micro-batches does not happen here: FusedAdamW(accum_steps=k) keeps the running
+sum in a second flat buffer (optim.AccumCycle), and every micro-batch opens a step of its own.
 Parameters the sink does not know go through autograd as usual."""
 from __future__ import annotations
 
@@ -42,8 +45,9 @@ class GradSink:
         if e is None or not p.requires_grad:
             return None
         if id(p) in self.written:
-            raise RuntimeError("GradSink: a parameter received two gradients in one step (weight sharing / "
-                               "gradient accumulation is not supported on the direct path)")
+            raise RuntimeError("GradSink: a parameter received two gradients in one micro-batch (weight sharing or a second "
+                               "backward pass before the next begin_step(): the kernels overwrite the buffer; to sum "
+                               "gradients over micro-batches use FusedAdamW(accum_steps=k))")
         return e[1]
 
     def done(self, p):

@@ -14,13 +14,29 @@ import torch
 from . import gradsink, ops, units
 from .ddp import BucketedAllReduce
 from .losses import kd_objective, kd_objective_backward
-from .optim import FusedAdamW
+from .optim import AccumCycle, FusedAdamW
 
 
 KD_FEATURES = ("camera_feat", "lidar_feat", "logits")       # what the objective reads of each model's intermediates
 
 
-class KDStep:
+class _TakesAccumSteps(type):
+    """`KDStep(..., accum_steps=k)`: a keyword-only option taken here, so that KDStep.__init__ keeps the argument list callers
+    and tests/test_gpu_region_loss.py pin, name for name.  None (the default) takes the optimiser's value."""
+
+    def __call__(cls, *args, accum_steps=None, **kw):
+        step = super().__call__(*args, **kw)
+        step.cycle = AccumCycle(step.opt, step.reducer, accum_steps)
+        return step
+
+
+class KDStep(metaclass=_TakesAccumSteps):
+    """Gradient accumulation: with FusedAdamW(accum_steps=k), k > 1, every call is ONE micro-batch.  Calls 1 .. k-1 of a cycle run
+    forward and backward and add the gradients to the optimiser's accumulation buffer (no update, no collective;
+    parts["stepped"] is False); call k folds the sum into the gradient buffer and steps on it with 1/k (parts["stepped"] is
+    True).  BatchNorm statistics are per micro-batch, as in torch.  `flush()` steps a partial cycle.  `accum_steps=k` on this
+    constructor only cross-checks the optimiser, which owns the buffer: a different value raises ValueError."""
+
     def __init__(self, student, teacher, optimizer: FusedAdamW, class_weights: Optional[torch.Tensor] = None,
                  T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
                  reducer: Optional[BucketedAllReduce] = None, teacher_storage: str = "fp32",
@@ -65,7 +81,12 @@ class KDStep:
             raise RuntimeError("a deposited feature gradient was not collected (kdrt.gradsink): set KD_GRAD_ROUTING=0")
         return total.detach(), parts
 
+    def flush(self) -> bool:
+        """Step on a partial cycle (j < k accumulated micro-batches, divisor j) -> whether a step was made"""
+        return self.cycle.flush()
+
     def __call__(self, images, points, labels):
+        self.cycle.begin()
         units.share_point_bins(True)       # teacher and student of THIS step sort the same points once ...
         try:
             zt, mt = self.teacher_forward(images, points)
@@ -77,9 +98,10 @@ class KDStep:
             units.share_point_bins(False)  # ... and nothing of it outlives the two forward passes
         total, parts = self.objective_backward(zs, ms, zt, mt, labels)
         self.sink.end_step()
-        self.opt.grad_scale = self.reducer.finish() if self.reducer is not None else 1.0
-        self.opt.step()
-        if self.opt.max_grad_norm is not None:
+        stepped = self.cycle.finish()
+        if self.cycle.k > 1:
+            parts["stepped"] = stepped
+        if stepped and self.opt.max_grad_norm is not None:
             parts["grad_norm"] = self.opt.last_grad_norm      # device scalar (pre-clip norm of the applied gradient): no sync
         parts["total"] = total
         parts["logits"] = zs.detach()
@@ -100,6 +122,11 @@ class GraphedKDStep:
     The capture then runs in "thread_local" error mode (the process group's watchdog thread polls events of earlier
     collectives from another thread, which the default "global" mode would treat as a capture violation).
 
+    Over a KDStep with gradient accumulation (accum_steps = k > 1) the graph holds one whole CYCLE: the static buffers and
+    `__call__` take k * B frames, the captured body runs the k micro-batches on consecutive slices of B frames (k - 1
+    accumulations, one fold, one AdamW update), and a replay is one optimiser step.  The returned parts are those of the last
+    micro-batch, except "logits" (all k * B frames) and "total" (the mean of the k micro-batch losses).  Not with a reducer.
+
     Restrictions: fixed batch shape; `optimizer.sync_lr()` happens automatically before each replay; more than one rank is
     an explicit opt-in (see __init__)."""
 
@@ -112,13 +139,21 @@ class GraphedKDStep:
         if world > 1 and not (allow_multi_rank or os.environ.get("KD_GRAPH_MULTI_RANK") == "1"):
             raise RuntimeError(f"GraphedKDStep: capturing the gradient all-reduces of a {world}-rank job has not run on hardware "
                                "yet; pass allow_multi_rank=True (or KD_GRAPH_MULTI_RANK=1) to try it, or use the eager KDStep")
+        self.k = k = step.cycle.k
+        if k > 1 and step.reducer is not None:
+            raise RuntimeError("GraphedKDStep: gradient accumulation (accum_steps > 1) together with a gradient reducer inside a "
+                               "capture is not supported; use the eager KDStep")
+        if k > 1 and (step.cycle.pending or images.shape[0] % k):
+            raise RuntimeError(f"GraphedKDStep: accum_steps={k} needs k * B frames ({images.shape[0]} given) and a KDStep at the "
+                               "start of a cycle")
         self.step = step
         self.images, self.points, self.labels = images.clone(), points.clone(), labels.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                       # warm-up on a side stream (allocator, workspaces, caches)
             for _ in range(warmup):
-                self.out = step(self.images, self.points, self.labels)
+                for im, pt, lb in self._micro_batches():    # (whole cycles: the capture starts at the beginning of one)
+                    self.out = step(im, pt, lb)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -128,21 +163,37 @@ class GraphedKDStep:
             self.out = self._body()
         self.replays = 0
 
+    def _micro_batches(self):
+        """the static buffers as k slices of B frames (k == 1: the buffers themselves)"""
+        if self.k == 1:
+            return [(self.images, self.points, self.labels)]
+        B = self.images.shape[0] // self.k
+        return [(self.images[j * B:(j + 1) * B], self.points[j * B:(j + 1) * B], self.labels[j * B:(j + 1) * B]) for j in range(self.k)]
+
     def _body(self):
         s = self.step
-        zt, mt = s.teacher_forward(self.images, self.points)
-        gradsink.active = s.sink
-        s.sink.begin_step()
-        s.opt.zero_grad()
-        zs, ms = s.student(self.images, self.points, return_intermediates=KD_FEATURES)
-        total, parts = s.objective_backward(zs, ms, zt, mt, self.labels)
-        s.sink.end_step()
-        s.opt.grad_scale = s.reducer.finish() if s.reducer is not None else 1.0
-        s.opt.enqueue_update()
+        totals, logits = [], []
+        for images, points, labels in self._micro_batches():
+            s.cycle.begin()
+            zt, mt = s.teacher_forward(images, points)
+            gradsink.active = s.sink
+            s.sink.begin_step()
+            s.opt.zero_grad()
+            zs, ms = s.student(images, points, return_intermediates=KD_FEATURES)
+            total, parts = s.objective_backward(zs, ms, zt, mt, labels)
+            s.sink.end_step()
+            stepped = s.cycle.finish(enqueue_only=True)
+            totals.append(total)
+            logits.append(zs.detach())
         if s.opt.max_grad_norm is not None:
             parts["grad_norm"] = s.opt.last_grad_norm
-        parts["total"] = total
-        parts["logits"] = zs.detach()
+        if self.k > 1:
+            parts["stepped"] = stepped
+            parts["total"] = torch.stack(totals).mean()
+            parts["logits"] = torch.cat(logits)
+        else:
+            parts["total"] = total
+            parts["logits"] = zs.detach()
         return parts
 
     def __call__(self, images=None, points=None, labels=None):

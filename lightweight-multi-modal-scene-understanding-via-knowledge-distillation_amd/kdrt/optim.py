@@ -17,6 +17,12 @@ buffer looks its group up in a segment table, and the averaged copy is updated f
 Both live on the device, so a captured graph of the step follows a scheduler and the EMA warm-up on replay.  With one group and
 no EMA the optimiser calls exactly kd_adamw_step_dev / kd_adamw_step_clip_dev, as before.  `decay_groups` builds the usual
 groups: no weight decay on BatchNorm parameters and biases, a learning-rate multiplier per top-level module.
+
+Gradient accumulation (`accum_steps=k`, 1 by default): backward kernels OVERWRITE their slot of the flat gradient buffer, so the
+sum over the k micro-batches of a cycle lives in a second flat buffer, `flat.accum`.  `accumulate()` adds the gradient buffer
+to it after each of the first k-1 micro-batches; `fold()` after the last writes accum + grad into the gradient buffer and zeroes
+accum in the same pass (kd_grad_accumulate), and the step is then the unchanged AdamW entry point on the summed gradient with
+`grad_scale / k`.  `AccumCycle` is the bookkeeping KDStep and Trainer share.  With k == 1 nothing is allocated and no call is added.
 """
 from __future__ import annotations
 
@@ -43,6 +49,7 @@ class FlatParams:
         self.numel = self.offsets[-1]
         self.data = torch.zeros(self.numel, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(self.numel, device=dev, dtype=torch.float32)
+        self.accum: Optional[torch.Tensor] = None        # FusedAdamW(accum_steps > 1): the running sum over micro-batches
         for p, o in zip(self.params, self.offsets):
             n = p.numel()
             self.data[o:o + n].copy_(p.data.reshape(-1))
@@ -77,10 +84,17 @@ def decay_groups(model: torch.nn.Module, lr: float, weight_decay: float, lr_mult
     return list(groups.values())
 
 
+def check_accum_steps(k) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"accum_steps must be an int >= 1, got {k!r}")
+    return k
+
+
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, flat_order=None,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, accum_steps=1):
         params = list(params)
+        self.accum_steps = check_accum_steps(accum_steps)
         if max_grad_norm is not None and not (math.isfinite(float(max_grad_norm)) and float(max_grad_norm) > 0):
             raise ValueError(f"max_grad_norm must be None or a finite value > 0, got {max_grad_norm!r}")
         if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
@@ -98,6 +112,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                        or len(order) != len({id(p) for p in order})):
             raise ValueError("flat_order must list exactly the parameters of the groups, each once")
         self.flat = FlatParams(order)
+        if self.accum_steps > 1:
+            self.flat.accum = torch.zeros_like(self.flat.grad)
         self.exp_avg = torch.zeros_like(self.flat.data)
         self.exp_avg_sq = torch.zeros_like(self.flat.data)
         self._step = 0
@@ -154,6 +170,25 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def zero_grad(self, set_to_none: bool = False):
         self.flat.zero_grad()
+
+    # ---- gradient accumulation ---------------------------------------------------------------------------------------------
+    def _need_accum(self):
+        if self.flat.accum is None:
+            raise RuntimeError("this needs FusedAdamW(accum_steps=k) with k > 1: no accumulation buffer is kept")
+
+    def accumulate(self):
+        """accum += grad over the whole buffer (after each micro-batch of a cycle but the last); one launch"""
+        self._need_accum()
+        lib.call("kd_grad_accumulate", P(self.flat.accum), P(self.flat.grad), self.flat.numel, 0, stream())
+
+    def fold(self, lo: Optional[int] = None, hi: Optional[int] = None):
+        """grad = accum + grad and accum = 0 over the whole buffer, or over the floats [lo, hi) of it (a gradient bucket: tensor
+        starts, so 16-byte aligned).  After the last micro-batch of a cycle, once per element, before the step."""
+        self._need_accum()
+        lo, hi = 0 if lo is None else int(lo), self.flat.numel if hi is None else int(hi)
+        if not 0 <= lo <= hi <= self.flat.numel:
+            raise ValueError(f"fold: [{lo}, {hi}) is not a slice of the {self.flat.numel} floats of the flat buffer")
+        lib.call("kd_grad_accumulate", P(self.flat.accum[lo:hi]), P(self.flat.grad[lo:hi]), hi - lo, 1, stream())
 
     def sync_lr(self):
         """Push the current learning rate to the device state (call after a scheduler step; cheap no-op otherwise).  With
@@ -299,3 +334,73 @@ class FusedAdamW(torch.optim.Optimizer):
         self.epoch += 1
         self.dev_state[1:2].fill_(float(self._step))
         self._dev_lr = self._dev_groups = None
+
+
+class AccumCycle:
+    """The k-micro-batch cycle of a training step's owner (KDStep, Trainer): which call accumulates, which folds and steps.
+
+    begin() before a micro-batch's backward pass says whether it is the last of its cycle and, under data parallelism, opens the
+    reducer for that one only (the hooks stay silent on the others: one set of collectives per optimiser step).  finish() after
+    the backward pass accumulates (-> False) or folds, sets `grad_scale = (1 / world) * (1 / k)` and steps (-> True); with a
+    reducer every bucket is folded by the reducer itself the moment its last gradient lands (BucketedAllReduce.fold), before its
+    all-reduce.  flush() steps a partial cycle of j < k micro-batches with divisor j.  With k == 1 finish() is the step as it was:
+    `grad_scale = reducer.finish()` or 1, `opt.step()`."""
+
+    def __init__(self, opt: "FusedAdamW", reducer=None, accum_steps: Optional[int] = None):
+        k = opt.accum_steps if accum_steps is None else check_accum_steps(accum_steps)
+        if k != opt.accum_steps:
+            raise ValueError(f"accum_steps={k} disagrees with the optimiser's accum_steps={opt.accum_steps}: build "
+                             f"FusedAdamW(accum_steps={k}), which owns the accumulation buffer")
+        self.opt, self.reducer, self.k = opt, reducer, k
+        self.pending = 0                   # micro-batches accumulated since the last optimiser step
+        self.final = True
+        if reducer is not None and k > 1:
+            reducer.fold = opt.fold
+
+    def begin(self) -> bool:
+        self.final = self.pending == self.k - 1
+        if self.reducer is not None and self.k > 1:
+            self.reducer.enabled = self.final
+        return self.final
+
+    def _update(self, scale: float, enqueue_only: bool):
+        self.opt.grad_scale = scale
+        if enqueue_only:                   # inside a graph capture: the host bookkeeping happens per replay
+            self.opt.enqueue_update()
+        else:
+            self.opt.step()
+
+    def finish(self, enqueue_only: bool = False) -> bool:
+        if self.k == 1:
+            self._update(self.reducer.finish() if self.reducer is not None else 1.0, enqueue_only)
+            return True
+        if not self.final:
+            self.opt.accumulate()
+            self.pending += 1
+            return False
+        if self.reducer is not None:
+            scale = self.reducer.finish()  # folds (and reduces) every bucket the hooks have not launched yet
+        else:
+            self.opt.fold()
+            scale = 1.0
+        self.pending = 0
+        self._update(scale * (1.0 / self.k), enqueue_only)
+        return True
+
+    def flush(self) -> bool:
+        """Step on the j < k micro-batches accumulated so far (divisor j); nothing pending: nothing happens.  Every rank of a
+        data-parallel job must call it at the same point (their loaders give them the same number of batches)."""
+        j = self.pending
+        if j == 0:
+            return False
+        self.opt.zero_grad()               # the last micro-batch's gradient is in accum already: the fold adds zeros to it
+        if self.reducer is not None:
+            self.reducer.enabled = True
+            self.reducer.reset()
+            scale = self.reducer.finish()
+        else:
+            self.opt.fold()
+            scale = 1.0
+        self.pending = 0
+        self._update(scale * (1.0 / j), False)
+        return True

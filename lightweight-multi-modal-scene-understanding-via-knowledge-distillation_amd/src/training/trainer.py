@@ -23,7 +23,7 @@ from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
 from kdrt.losses import RegionLoss, confusion, region_seg_loss, seg_loss
-from kdrt.optim import FusedAdamW, decay_groups
+from kdrt.optim import AccumCycle, FusedAdamW, check_accum_steps, decay_groups
 
 try:
     from tqdm import tqdm
@@ -34,7 +34,8 @@ except ImportError:  # pragma: no cover
 
 def optim_options_from_env(env=None):
     """Trainer keywords from the entry scripts' switches: KD_EMA_DECAY=0.999, KD_EMA_WARMUP=1, KD_NO_DECAY_NORM_BIAS=1,
-    KD_LR_MULT="camera_encoder=0.1,lidar_encoder=0.5".  Nothing set: {} -- the scripts then build the trainer exactly as before."""
+    KD_LR_MULT="camera_encoder=0.1,lidar_encoder=0.5", KD_ACCUM_STEPS=4 (an integer >= 1: loader batches per optimiser step).
+    Nothing set: {} -- the scripts then build the trainer exactly as before."""
     env = os.environ if env is None else env
     kw = {}
     if env.get("KD_EMA_DECAY"):
@@ -52,6 +53,12 @@ def optim_options_from_env(env=None):
                 raise ValueError(f"KD_LR_MULT must look like 'camera_encoder=0.1,head=2', got {env['KD_LR_MULT']!r}")
             mult[name.strip()] = float(val)
         kw["lr_mult"] = mult
+    if env.get("KD_ACCUM_STEPS"):
+        try:
+            k = int(env["KD_ACCUM_STEPS"])
+        except ValueError:
+            raise ValueError(f"KD_ACCUM_STEPS must be an integer >= 1, got {env['KD_ACCUM_STEPS']!r}") from None
+        kw["accum_steps"] = check_accum_steps(k)
     return kw
 
 
@@ -103,7 +110,7 @@ class SegmentationMetrics:
 
 class Trainer:
     def __init__(self, model, train_loader, val_loader, device, lr=1e-3, weight_decay=1e-3, save_dir="checkpoints",
-                 class_weights=None, num_epochs=20, max_grad_norm=None, ema_decay=None, ema_warmup=False,
+                 class_weights=None, num_epochs=20, accum_steps=1, max_grad_norm=None, ema_decay=None, ema_warmup=False,
                  no_decay_norm_bias=False, lr_mult=None, hard_loss=None):
         self.model = model
         self.train_loader = train_loader
@@ -130,8 +137,13 @@ class Trainer:
         params = model.parameters()
         if no_decay_norm_bias or lr_mult:
             params = decay_groups(model, lr, weight_decay, lr_mult, no_decay=bool(no_decay_norm_bias))
+        # Gradient accumulation (accum_steps = k > 1): every loader batch is one micro-batch, an optimiser step is made on every
+        # k-th (and on what is left when the loader is exhausted), on the mean of the k gradients; BatchNorm statistics, the loss
+        # and the metrics stay per batch.  Under data parallelism the gradients are reduced once per optimiser step.
+        self.accum_steps = check_accum_steps(accum_steps)
         self.optimizer = FusedAdamW(params, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                                    flat_order=model.parameters(), ema_decay=ema_decay, ema_warmup=ema_warmup)
+                                    flat_order=model.parameters(), ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                    accum_steps=self.accum_steps)
         self.scheduler = optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=num_epochs, eta_min=1e-5)
         # Data parallel (torch.distributed initialised, world > 1): every rank starts from rank 0's weights and the
         # gradients are summed over ranks in buckets as backward produces them (kdrt.ddp), for plain CE training as for KD.
@@ -146,6 +158,8 @@ class Trainer:
         if class_weights is not None:
             self._log(f"Using class weights: {class_weights.tolist()}")
         self.sink = gradsink.install(self.optimizer.flat, self.reducer)   # backward kernels write into the flat grad buffer
+        self.cycle = AccumCycle(self.optimizer, self.reducer)
+        self.stepped = True              # whether the last _step() made an optimiser step (always, without accumulation)
         self.save_dir = save_dir
         self.epoch = 0
         if self.is_main:
@@ -175,8 +189,9 @@ class Trainer:
         if self.is_main:
             print(*a, **k)
 
-    # one optimisation step; overridden by KDTrainer
+    # one loader batch: an optimisation step, or with accum_steps > 1 a micro-batch of one; overridden by KDTrainer
     def _step(self, imgs, pts, seg):
+        self.cycle.begin()
         gradsink.active = self.sink
         self.sink.begin_step()           # (also drops anything an earlier step that failed half-way -- a caught OOM -- left deposited)
         self.optimizer.zero_grad()
@@ -187,9 +202,15 @@ class Trainer:
             gradsink.drop_pending()
             raise RuntimeError("a deposited feature gradient was not collected (kdrt.gradsink): unsupported model structure; set KD_GRAD_ROUTING=0")
         self.sink.end_step()
-        self.optimizer.grad_scale = self.reducer.finish() if self.reducer is not None else 1.0
-        self.optimizer.step()
+        self.stepped = self.cycle.finish()
         return loss.detach(), logits.detach()
+
+    def flush(self):
+        """Step on a partial accumulation cycle (fewer than accum_steps batches since the last optimiser step), dividing by
+        their number -> whether a step was made.  train_epoch calls it when the loader is exhausted: no gradient crosses an
+        epoch or reaches a checkpoint."""
+        self.stepped = self.cycle.flush()
+        return self.stepped
 
     def _mean_over_ranks(self, total, n_batches):
         """(sum of per-batch losses, batch count) -> mean over every rank's batches."""
@@ -204,6 +225,7 @@ class Trainer:
         metrics = SegmentationMetrics(num_classes=2, device=self.device)
         total = torch.zeros((), device=self.device)
         gnorm = torch.zeros((), device=self.device) if self.max_grad_norm is not None else None
+        steps = 0
         if hasattr(self.train_loader, "set_epoch"):       # rank-sharded loaders reshuffle per epoch, identically on all ranks
             self.train_loader.set_epoch(self.epoch)
         for batch in tqdm(self.train_loader, desc="Train", disable=not self.is_main):
@@ -212,11 +234,16 @@ class Trainer:
             seg = batch["segmentation"].to(self.device, non_blocking=True)
             loss, logits = self._step(imgs, pts, seg)
             total += loss                      # stays on the device: no per-step sync
-            if gnorm is not None:
+            if gnorm is not None and self.stepped:
                 gnorm += self.optimizer.last_grad_norm
+                steps += 1
             metrics.update(logits, seg)
+        if self.flush() and gnorm is not None:
+            gnorm += self.optimizer.last_grad_norm
+            steps += 1
         if gnorm is not None:                  # identical on every rank: no mean over ranks (a skipped step's inf / NaN shows here)
-            self.last_epoch_grad_norm = gnorm.item() / max(len(self.train_loader), 1)
+            # the mean over optimiser steps (without accumulation: one per loader batch, the divisor as it was)
+            self.last_epoch_grad_norm = gnorm.item() / max(steps if self.accum_steps > 1 else len(self.train_loader), 1)
         return self._mean_over_ranks(total, len(self.train_loader)), metrics.compute()
 
     def validate(self):
@@ -327,7 +354,9 @@ class KDTrainer(Trainer):
         self.kd_step = KDStep(model, teacher, self.optimizer, self.class_weights, T, alpha, beta, self.ignore_index, self.reducer,
                               hard_loss=self.hard_loss)
         self.sink = self.kd_step.sink
+        self.cycle = self.kd_step.cycle         # one cycle: the KD step's (flush() goes to it)
 
     def _step(self, imgs, pts, seg):
         parts = self.kd_step(imgs, pts, seg)
+        self.stepped = parts.get("stepped", True)
         return parts["total"], parts["logits"]

@@ -4,7 +4,8 @@ train_pandaset.py:79-163), on the MI355X-native path.  KD_DATA_ROOT overrides th
 KD_LOADER_AUGMENT="rot=5,flip=0.5,jitter=0.02,..." turns the opt-in training augmentation on (training loader only;
 create_pandaset_dataloaders reads it, nothing changes here).
 KD_EMA_DECAY=0.999 (with KD_EMA_WARMUP=1) validates and checkpoints an EMA of the weights, KD_NO_DECAY_NORM_BIAS=1 takes the weight
-decay off BatchNorm parameters and biases, KD_LR_MULT="camera_encoder=0.1,..." scales the learning rate per top-level module
+decay off BatchNorm parameters and biases, KD_LR_MULT="camera_encoder=0.1,..." scales the learning rate per top-level module, KD_ACCUM_STEPS=4 makes one optimiser step per
+4 loader batches on the mean of their gradients (gradient accumulation: BatchNorm statistics stay per batch)
 (src.training.trainer.optim_options_from_env); all unset: nothing changes."""
 import os
 

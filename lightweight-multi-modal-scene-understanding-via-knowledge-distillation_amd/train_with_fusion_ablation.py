@@ -15,6 +15,8 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
                  KD_EMA_VALIDATE_LIVE=1 also validates the live weights (history "val_miou_live")
   KD_NO_DECAY_NORM_BIAS   1: no weight decay on BatchNorm parameters and biases (every parameter with ndim <= 1)
   KD_LR_MULT     "camera_encoder=0.1,...": learning-rate multiplier per top-level module of the model
+  KD_ACCUM_STEPS unset: 1.  k: gradient accumulation, one optimiser step per k loader batches on the mean of their gradients
+                 (BatchNorm statistics per batch; data parallel: one set of all-reduces per optimiser step, not per batch)
 Launch with `python -m torch.distributed.run --nproc-per-node N` for data-parallel training: one process per GPU,
 frames sharded over ranks in equal counts (every rank runs the same number of steps), rank 0's initial weights
 broadcast, gradients all-reduced in buckets during backward (CE and KD training alike), BatchNorm statistics per
@@ -80,7 +82,7 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
               class_weights=[0.4, 3.5], num_epochs=int(os.environ.get("KD_EPOCHS", 20)),
               max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None)
     kw["hard_loss"] = hard_loss_from_env()
-    kw.update(optim_options_from_env())        # KD_EMA_DECAY, KD_EMA_WARMUP, KD_NO_DECAY_NORM_BIAS, KD_LR_MULT: all unset = {}
+    kw.update(optim_options_from_env())        # KD_EMA_DECAY, KD_EMA_WARMUP, KD_NO_DECAY_NORM_BIAS, KD_LR_MULT, KD_ACCUM_STEPS: all unset = {}
     if kw["hard_loss"] is not None:
         log(f"  Hard-label loss: {kw['hard_loss']}")
     if teacher_ckpt:
