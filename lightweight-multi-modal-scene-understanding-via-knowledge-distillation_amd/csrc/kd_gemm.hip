@@ -1009,8 +1009,8 @@ int kd_lidar_l1_dgrad(const float* G, int64_t ldg, const float* Y1, int64_t ldy,
   const int sr = g_gemm_split.load(std::memory_order_relaxed) ? kd_gemm_stream_stat_rows(M, N1, K0, 2, 3, false) : 0;
   const int rc = gemm_launch(g, 2, 3, (hipStream_t)stream, partial_rows);
   if (rc || !m1_out) return rc;
-  // one slab row per wave of the streaming kernel, else per output tile: 256 rows when the output is at most 64 wide
-  // (see gemm_launch), else 128
+  // one moment-slab row per output tile of the tiled kernel: 256 rows when the output is at most 64 wide (see gemm_launch),
+  // else 128.  (stream_cfg has no instance for epi 3, so sr is 0 today and kd_lidar_l1_dgrad_stat_rows is the tiled count.)
   const bool tall = ((K0 - 1) % 128) < 64;
   const int nrb = sr > 0 ? sr : (int)(tall ? (M + 255) / 256 : (M + 127) / 128);
   return kd_slab_reduce_tall_launch((float*)m1_ws, nrb, (int64_t)4 * K0, m1_out, (hipStream_t)stream);

@@ -68,12 +68,13 @@ def stream_lds_bytes(K, N, pro):
 
 
 def stream_cfg(K, N, pro, epi, add):
-    """stream_cfg of kd_gemm_stream.hip in mode 2 (every covered shape) for pro 0 / 1 / 2 -> (kb, nb, ntiles) or None"""
+    """stream_cfg of kd_gemm_stream.hip in mode 2 (every covered shape) for pro 0 / 1 / 2 and the table-form data gradient of the
+    LiDAR branch (pro 4, epi 2: one instance, 128 -> 128) -> (kb, nb, ntiles) or None"""
     if K % 32 or N % 32:
         return None
     kb, nbt = K // 32, N // 32
     fwd = pro in (0, 1) and epi in (0, 1, 5)
-    bwd = pro == 2 and epi in (0, 2)
+    bwd = (pro == 2 and epi in (0, 2)) or (pro == 4 and epi == 2 and kb == 4 and nbt == 4)
     if not (fwd or bwd) or kb not in (1, 2, 4):
         return None
     nb = next((c for c in (4, 2, 1) if nbt % c == 0 and stream_lds_bytes(K, 32 * c, pro) <= LDS_MAX), 0)
