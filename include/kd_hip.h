@@ -480,6 +480,22 @@ int kd_seg_region_loss_fwd_bwd(const float* zs, const float* zt, const int64_t* 
                                float T, float alpha, float gscale, const float* gscale_dev, float gamma, float wf, float wt,
                                float a, float b, float s, float* vals, float* dzs, int B, int NC, int HW, void* ws,
                                size_t ws_bytes, void* stream);
+/* The opt-in Lovasz-Softmax hard-label term (csrc/kd_loss_lovasz.hip), classes = "present", per image:
+ *   L = (1/B) sum_b (1/|P_b|) sum_{c in P_b} L_{b,c},  L_{b,c} = sum_k e_k g_k over the kept pixels of image b (the pixels
+ *   kd_seg_loss_fwd_bwd keeps) sorted by the error e descending, equal fp32 bits in ascending pixel order; e = p_c off the class and
+ *   the sum of the other probabilities on it (p = softmax(zs)), g_k the increment of the Jaccard loss at sorted position k, P_b the
+ *   classes with a pixel in image b.  An image without a kept pixel adds 0 and still counts in B.  No class weights.
+ * vals holds 1 + 4 floats: L, then per class the mean of L_{b,c} over the images where it is present (0 if never).
+ * hard_inout (may be NULL): hard_inout[0] += weight * L.   dzs (may be NULL: forward only) = weight * gscale * gscale_dev[0] * dL/dzs,
+ * stored (accumulate = 0) or added to what dzs holds (accumulate = 1: the CE / region call wrote it before, on the same stream).
+ * order_out (may be NULL; for tests): [B][NC][HW] int32, the pixel at sorted position k, -1 past the kept count and for absent classes.
+ * One workgroup per (image, class) sorts 64-bit keys in LDS, so HW <= 16384 (128 x 128) and 2 <= NC <= 4, else KD_ERR_SHAPE; a
+ * weight that is not finite and > 0 or a NULL zs / target / vals is KD_ERR_ARG; ws = kd_seg_lovasz_ws_bytes(B, NC, HW) bytes, else
+ * KD_ERR_WORKSPACE.  Three launches, no atomics, no host reads: bit-identical from call to call. */
+size_t kd_seg_lovasz_ws_bytes(int B, int NC, int HW);
+int kd_seg_lovasz_fwd_bwd(const float* zs, const int64_t* target, int ignore_index, float weight, float gscale,
+                          const float* gscale_dev, float* vals, float* hard_inout, float* dzs, int accumulate, int32_t* order_out,
+                          int B, int NC, int HW, void* ws, size_t ws_bytes, void* stream);
 size_t kd_mse_ws_bytes(int64_t n);
 int kd_mse_fwd_bwd(const float* a, const float* b, int64_t n, float gcoef, const float* gscale_dev, float* loss,
                    float* da, void* ws, size_t ws_bytes, void* stream);

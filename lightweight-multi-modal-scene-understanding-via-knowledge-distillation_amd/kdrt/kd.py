@@ -54,6 +54,8 @@ class KDStep(metaclass=_TakesAccumSteps):
         self.cw, self.T, self.alpha, self.beta, self.ignore_index = class_weights, T, alpha, beta, ignore_index
         # hard_loss (kdrt.losses.RegionLoss): wf*Focal + wt*Tversky as the hard-label term instead of the weighted CE; None keeps
         # the CE.  Data parallel: the Tversky sums cover each rank's own shard, the reducer averages the per-rank gradients.
+        # A kdrt.losses.LovaszLoss adds weight * Lovasz-Softmax to its base term (the CE or a RegionLoss): a mean over images, so
+        # with equal shards the averaged per-rank gradient is the global batch's.
         self.hard_loss = hard_loss
         self.reducer = reducer
         self.sink = gradsink.install(optimizer.flat, reducer)      # backward kernels write into the flat grad buffer

@@ -4,6 +4,8 @@
                   teacher's logits -- value and dL/dlogits produced by one fused HIP call
   region_seg_loss : the opt-in hard-label loss wf*Focal + wt*Tversky (RegionLoss) in place of the weighted CE, same fused
                   form (csrc/kd_loss_region.hip; definition in DESIGN.md section 3)
+  lovasz_seg_loss : the opt-in Lovasz-Softmax term (LovaszLoss) added to the weighted CE or to a RegionLoss: the base call, then
+                  csrc/kd_loss_lovasz.hip on the same stream, adding its value and its gradient to what the base call wrote
   feature_mse   : F.mse_loss forward + gradient
   kd_objective  : CE + alpha*T^2*KL + beta*(MSE(cam) + MSE(lidar))   (the
                   reference has no KD code -- this definition is the build's specification)
@@ -191,6 +193,108 @@ def region_seg_loss(logits, target, spec: RegionLoss, class_weights: Optional[to
     return hard, kl, {"focal": focal, "tversky": tversky, "class_ti": class_ti}
 
 
+@dataclass(frozen=True)
+class LovaszLoss:
+    """The Lovasz-Softmax hard-label term (Berman et al., CVPR 2018) on top of a base term:
+
+      L_hard = base + weight * Lovasz,    base: None (the weighted CE) or a RegionLoss
+      Lovasz = (1/B) sum_b (1/|P_b|) sum_{c in P_b} L_{b,c}      classes = "present", per image
+
+    L_{b,c} sorts the kept pixels of image b by the class's error (p_c off the class, the sum of the other probabilities on it)
+    descending -- equal fp32 errors in ascending pixel order, so the gradient is a function of the input -- and weighs them with
+    the increments of the Jaccard loss along that order.  P_b: the classes with a kept pixel in image b; an image without one
+    adds 0 and still counts in B.  Class weights do not enter.  One workgroup sorts an image's keys in LDS: H * W <= 16384
+    (128 x 128), KDError above.
+    The term is a mean over images: with equal shards under data parallelism the mean of the per-rank losses IS the loss of the
+    global batch and the reducer's averaged gradient its gradient (the batch-wide Tversky sums of RegionLoss lack this)."""
+    weight: float = 1.0
+    base: Optional[RegionLoss] = None
+
+    def __post_init__(self):
+        w = self.weight
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w <= 0:
+            raise ValueError(f"LovaszLoss: weight must be a finite number > 0, got {w!r}")
+        if self.base is not None and not isinstance(self.base, RegionLoss):
+            raise ValueError(f"LovaszLoss: base must be a RegionLoss or None (the weighted CE), got {type(self.base).__name__}")
+
+
+LOVASZ_VALS = 5           # floats kd_seg_lovasz_fwd_bwd writes: L, then per class the mean of L_{b,c} over the images where it is present
+LOVASZ_MAX_HW = 16384     # 8-byte keys of one image in the LDS of one CU
+
+
+def _lovasz_call(spec, zs, target, ignore_index, gdev, vals, hard, dzs):
+    """the Lovasz call that follows the base call on the same stream: hard[0] += weight * L, dzs += weight * gdev[0] * dL/dzs"""
+    B, NC, H, W = zs.shape
+    if H * W > LOVASZ_MAX_HW:
+        raise KDError(f"LovaszLoss: a {H} x {W} map has {H * W} pixels per image, the per-image sort holds at most {LOVASZ_MAX_HW} (128 x 128)")
+    nbytes = lib.kd_seg_lovasz_ws_bytes(B, NC, H * W)
+    ws = ops.workspace(nbytes, zs.device)
+    lib.call("kd_seg_lovasz_fwd_bwd", P(zs), P(target), int(ignore_index), float(spec.weight), 1.0, P(gdev), P(vals), P(hard), P(dzs),
+             1, None, B, NC, H * W, P(ws), nbytes, stream())
+
+
+def _hard_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, lov, dzs):
+    """base call (weighted CE or region loss) into hard / dzs, then the Lovasz call adding to both.  hard: REGION_VALS floats
+    ([0] the hard-label term, [1] KL in either layout), lov: LOVASZ_VALS floats."""
+    if spec.base is None:
+        _SegLossFn._call(zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, dzs)
+    else:
+        _region_call(spec.base, zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, dzs)
+    _lovasz_call(spec, zs, target, ignore_index, gdev, lov, hard, dzs)
+
+
+class _LovaszLossFn(torch.autograd.Function):
+    """_SegLossFn / _RegionLossFn with the Lovasz term added: the two calls of the fused objective, forward values only, backward
+    both again with the gradient."""
+
+    @staticmethod
+    def forward(ctx, zs, zt, target, class_w, ignore_index, T, alpha, spec):
+        ops.require_gpu_tensor(zs, "lovasz_seg_loss")
+        if not isinstance(spec, LovaszLoss):
+            raise KDError(f"lovasz_seg_loss: spec must be a kdrt.losses.LovaszLoss, got {type(spec).__name__}")
+        zs_c = zs.detach().contiguous()
+        zt_c = None if zt is None else zt.detach().contiguous()
+        target = target.contiguous()
+        if target.dtype != torch.int64:
+            raise KDError("segmentation target must be int64")
+        _check_target(zs_c, target)
+        _check_class_weights(zs_c, class_w)
+        hard = torch.zeros(REGION_VALS, device=zs.device, dtype=torch.float32)
+        lov = torch.empty(LOVASZ_VALS, device=zs.device, dtype=torch.float32)
+        _hard_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, hard, lov, None)
+        ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec)
+        kl, focal, tversky, lovasz, class_lovasz = hard[1], hard[3], hard[4], lov[0], lov[1:1 + zs_c.shape[1]]
+        ctx.mark_non_differentiable(kl, focal, tversky, lovasz, class_lovasz)
+        return hard[0], kl, focal, tversky, lovasz, class_lovasz
+
+    @staticmethod
+    def backward(ctx, g_hard, *_):
+        # the gradient through `hard` is d(L_hard + alpha*T^2*KL)/dzs (kd_objective adds KL's value separately)
+        zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec = ctx.args
+        hard = torch.empty(REGION_VALS, device=zs_c.device, dtype=torch.float32)
+        lov = torch.empty(LOVASZ_VALS, device=zs_c.device, dtype=torch.float32)
+        dzs = torch.empty_like(zs_c)
+        _hard_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, g_hard.contiguous().view(1), hard, lov, dzs)
+        return dzs, None, None, None, None, None, None, None
+
+
+def lovasz_seg_loss(logits, target, spec: LovaszLoss, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
+                    teacher_logits: Optional[torch.Tensor] = None, T: float = 4.0, alpha: float = 1.0):
+    """-> (hard, kl, parts): seg_loss / region_seg_loss with hard = base + spec.weight * Lovasz (see LovaszLoss; the class weights
+    enter the base term only).  The gradient that flows back through `hard` is that of hard + alpha*T^2*kl.
+    parts = {"lovasz", "class_lovasz"}: the unweighted Lovasz value and the [NC] vector of per-class means of L_{b,c} over the
+    images where the class is present (0 if never), detached; with a RegionLoss base also its "focal" and "tversky".
+    Data parallel: the Lovasz term is a mean over images, so with equal shards the mean of the per-rank values is the global one."""
+    if teacher_logits is None:
+        alpha = 0.0
+    hard, kl, focal, tversky, lovasz, class_lovasz = _LovaszLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T,
+                                                                         alpha, spec)
+    parts = {"lovasz": lovasz, "class_lovasz": class_lovasz}
+    if spec.base is not None:
+        parts.update(focal=focal, tversky=tversky)
+    return hard, kl, parts
+
+
 class _MSEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -223,13 +327,17 @@ def feature_mse(student_feat, teacher_feat):
 
 def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
                  class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
-                 hard_loss: Optional[RegionLoss] = None):
+                 hard_loss=None):
     """total = CE + alpha*T^2*KL + beta*(MSE(camera_feat) + MSE(lidar_feat)); returns (total, parts).
     hard_loss (a RegionLoss): wf*Focal + wt*Tversky takes the CE's place; parts["ce"] then carries it and parts gains "focal"
-    and "tversky".  Under data parallelism the Tversky sums cover this rank's shard (see RegionLoss)."""
+    and "tversky".  Under data parallelism the Tversky sums cover this rank's shard (see RegionLoss).
+    hard_loss (a LovaszLoss): weight * Lovasz is added to its base term (the CE or a RegionLoss); parts["ce"] carries the sum and
+    parts gains "lovasz" and "class_lovasz" (and the base's "focal" / "tversky").  A mean over images: exact under data parallelism."""
     extra = {}
     if hard_loss is None:
         ce, kl = seg_loss(student_logits, target, class_weights, ignore_index, teacher_logits, T, alpha)
+    elif isinstance(hard_loss, LovaszLoss):
+        ce, kl, extra = lovasz_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
     else:
         ce, kl, rp = region_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
         extra = {"focal": rp["focal"], "tversky": rp["tversky"]}
@@ -242,9 +350,11 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
 
 def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
                           class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
-                          hard_loss: Optional[RegionLoss] = None):
+                          hard_loss=None):
     """kd_objective(...)[0].backward() in one: returns (total, parts) with the student's gradients already propagated.
-    hard_loss as in kd_objective: the region-loss call writes dL/dlogits together with L_hard / KL in the CE call's place.
+    hard_loss as in kd_objective: the region-loss call writes dL/dlogits together with L_hard / KL in the CE call's place; the
+    Lovasz call follows its base call on the same stream and adds its value and its gradient to what that call wrote, before the
+    final kernel reads the hard-label term (parts gains "lovasz"; "class_lovasz" comes from the autograd form only).
 
     Same values and the same gradient bits as the autograd formulation, fewer passes: the segmentation-loss call writes
     dL/dlogits together with CE / KL; each feature MSE writes its gradient in the pass that sums its value, and that
@@ -272,6 +382,13 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     if hard_loss is None:
         lib.call("kd_seg_loss_fwd_bwd", P(zs_c), P(zt_c), P(target), P(class_weights), int(ignore_index), float(T), float(alpha),
                  1.0, None, P(vals), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
+    elif isinstance(hard_loss, LovaszLoss):
+        hard = torch.zeros(REGION_VALS, device=dev, dtype=torch.float32)
+        lov = torch.empty(LOVASZ_VALS, device=dev, dtype=torch.float32)
+        _hard_call(hard_loss, zs_c, zt_c, target, class_weights, ignore_index, T, alpha, None, hard, lov, dzs)
+        extra = {"lovasz": lov[0]}
+        if hard_loss.base is not None:
+            extra.update(focal=hard[3], tversky=hard[4])
     else:
         _check_region_spec(hard_loss)
         hard = torch.empty(REGION_VALS, device=dev, dtype=torch.float32)

@@ -22,7 +22,7 @@ import torch.optim as optim
 from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
-from kdrt.losses import RegionLoss, confusion, region_seg_loss, seg_loss
+from kdrt.losses import LovaszLoss, RegionLoss, confusion, lovasz_seg_loss, region_seg_loss, seg_loss
 from kdrt.optim import AccumCycle, FusedAdamW, check_accum_steps, decay_groups
 
 try:
@@ -123,11 +123,15 @@ class Trainer:
         self.ignore_index = -1
         # hard_loss (kdrt.losses.RegionLoss): train AND validate with wf*Focal + wt*Tversky instead of the weighted CE (the class
         # weights then enter the focal term only).  Data parallel: the Tversky sums cover each rank's own shard of the batch.
-        if hard_loss is not None and not isinstance(hard_loss, RegionLoss):
-            raise ValueError(f"hard_loss must be a kdrt.losses.RegionLoss or None, got {type(hard_loss).__name__}")
+        # hard_loss (kdrt.losses.LovaszLoss): its base term (the weighted CE or a RegionLoss) + weight * Lovasz-Softmax, a mean over
+        # images (exact under data parallelism with equal shards); maps of at most 128 x 128 pixels.
+        if hard_loss is not None and not isinstance(hard_loss, (RegionLoss, LovaszLoss)):
+            raise ValueError(f"hard_loss must be a kdrt.losses.RegionLoss, a kdrt.losses.LovaszLoss or None, got {type(hard_loss).__name__}")
         self.hard_loss = hard_loss
         if hard_loss is None:
             self.criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
+        elif isinstance(hard_loss, LovaszLoss):
+            self.criterion = lambda logits, seg: lovasz_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
         else:
             self.criterion = lambda logits, seg: region_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
         # Parameter groups (no weight decay on BatchNorm parameters and biases, a learning-rate multiplier per top-level module)

@@ -10,6 +10,9 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
   KD_HARD_LOSS   unset: the reference's weighted cross-entropy.  `focal_tversky`: focal + Tversky as the hard-label term
                  (kdrt.losses.RegionLoss), for CE and KD training alike; KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA
                  override its gamma (2), false-positive weight (0.7) and false-negative weight (0.3)
+                 `ce_lovasz`: the weighted cross-entropy + KD_LOVASZ_WEIGHT (1.0) * Lovasz-Softmax (kdrt.losses.LovaszLoss: the
+                 direct surrogate of the Jaccard index, per image over the classes present; label maps of at most 128 x 128).
+                 `focal_tversky_lovasz`: the same term on top of the RegionLoss the three knobs above describe
   KD_EMA_DECAY   unset: off.  e.g. 0.999: keep an EMA of the weights inside the AdamW step; validation, best.pth and the
                  checkpoint's "ema_state" use it.  KD_EMA_WARMUP=1: d_t = min(decay, (1 + t) / (10 + t)).
                  KD_EMA_VALIDATE_LIVE=1 also validates the live weights (history "val_miou_live")
@@ -55,15 +58,21 @@ def build_model(fusion_type, fusion_out_channels, device, num_classes=2, base_ch
 
 
 def hard_loss_from_env(env=os.environ):
-    """KD_HARD_LOSS -> None (weighted CE) or the RegionLoss the KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA knobs describe"""
+    """KD_HARD_LOSS -> None (weighted CE), the RegionLoss the KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA knobs describe, or a
+    LovaszLoss of weight KD_LOVASZ_WEIGHT over either (`ce_lovasz`, `focal_tversky_lovasz`)"""
     name = env.get("KD_HARD_LOSS", "")
     if name in ("", "ce"):
         return None
-    if name != "focal_tversky":
-        raise ValueError(f"KD_HARD_LOSS must be unset, 'ce' or 'focal_tversky', got {name!r}")
-    from kdrt.losses import RegionLoss
-    return RegionLoss(gamma=float(env.get("KD_FOCAL_GAMMA", 2.0)), a=float(env.get("KD_TVERSKY_ALPHA", 0.7)),
-                      b=float(env.get("KD_TVERSKY_BETA", 0.3)))
+    if name not in ("focal_tversky", "ce_lovasz", "focal_tversky_lovasz"):
+        raise ValueError(f"KD_HARD_LOSS must be unset, 'ce', 'focal_tversky', 'ce_lovasz' or 'focal_tversky_lovasz', got {name!r}")
+    from kdrt.losses import LovaszLoss, RegionLoss
+    region = None
+    if name != "ce_lovasz":
+        region = RegionLoss(gamma=float(env.get("KD_FOCAL_GAMMA", 2.0)), a=float(env.get("KD_TVERSKY_ALPHA", 0.7)),
+                            b=float(env.get("KD_TVERSKY_BETA", 0.3)))
+    if name == "focal_tversky":
+        return region
+    return LovaszLoss(weight=float(env.get("KD_LOVASZ_WEIGHT", 1.0)), base=region)
 
 
 def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, val_scenes, device):
