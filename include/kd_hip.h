@@ -509,6 +509,23 @@ int64_t kd_mse_slab_blocks(int64_t n);
 int kd_mse_partial(const float* a, const float* b, int64_t n, float gcoef, float* da, float* slab, void* stream);
 int kd_kd_objective_final(const float* ce_kl, const float* slab_c, int64_t n_c, const float* slab_l, int64_t n_l, float ckl, float beta,
                           float* out, void* stream);
+/* The opt-in channel-wise distillation feature term (csrc/kd_loss_cwd.hip; Shu et al., ICCV 2021) of two NHWC
+ * feature matrices s, t [B*HW, C] (row-major, what ops.nhwc_view yields), temperature tau:
+ *   phi(X)[b,c,i] = exp(X[b,i,c]/tau) / sum_j exp(X[b,j,c]/tau)   over the HW rows i, j of image b: a softmax down each COLUMN,
+ *   val[0] = tau^2 / (B*C) * sum_{b,c} sum_i phi(t) (log phi(t) - log phi(s))     (not scaled by gcoef),
+ *   ds     = k * (phi(s) - phi(t)),  k = gcoef * (gscale_dev ? gscale_dev[0] : 1) formed once in fp32 (ds NULL: forward only); the
+ *   caller passes gcoef = tau / (B*C) times whatever it folds in.
+ * Log-probabilities are x/tau - max - log(sum exp(x/tau - max)), never the logarithm of a probability; a position whose phi(t)
+ * underflows adds exactly 0.  stats_out (may be NULL; for tests): [B][C][4] = the column maximum M of s/tau and log(sum exp(s/tau - M)) (the
+ * log-sum-exp of the column is their sum, which the kernel never forms), then the same two of t/tau.  s and t go through the same instruction sequence: identical bits in both give val[0] == 0 and ds == +-0 exactly (s == t as
+ * pointers is allowed).  An image's statistics and ds rows depend on that image's rows and k alone (a B = 1 call on image b
+ * reproduces their bits).  C % 4 != 0, C > 512, HW < 1 or B < 1 is KD_ERR_SHAPE; a tau that is not finite and > 0 or a NULL s / t /
+ * val / ws is KD_ERR_ARG; s, t, ds or ws not 16-byte aligned is KD_ERR_ALIGN; ws = kd_feat_cwd_ws_bytes(B, HW, C) bytes, else
+ * KD_ERR_WORKSPACE.  Three launches (column statistics per row chunk; chunk join + the point-wise pass; the value's final sum in
+ * double), 5 sweeps of a map with the gradient and 4 without, no atomics, no host reads: bit-identical from call to call. */
+size_t kd_feat_cwd_ws_bytes(int B, int HW, int C);
+int kd_feat_cwd_fwd_bwd(const float* s, const float* t, int B, int HW, int C, float tau, float gcoef, const float* gscale_dev,
+                        float* val, float* ds, float* stats_out, void* ws, size_t ws_bytes, void* stream);
 /* pred[B*HW] = argmax over the NC (1..4) classes, first maximum wins; conf[M*M] (ACCUMULATED into) counts a pixel at [t, argmax]
  * when t != ignore_index and 0 <= t < M and argmax < M: M (1..4) is the width of the matrix, independent of NC.  Either of conf
  * and pred may be NULL; target NULL: no counting. */

@@ -13,7 +13,7 @@ import torch
 
 from . import gradsink, ops, units
 from .ddp import BucketedAllReduce
-from .losses import kd_objective, kd_objective_backward
+from .losses import ChannelKD, kd_objective, kd_objective_backward
 from .optim import AccumCycle, FusedAdamW
 
 
@@ -21,11 +21,17 @@ KD_FEATURES = ("camera_feat", "lidar_feat", "logits")       # what the objective
 
 
 class _TakesAccumSteps(type):
-    """`KDStep(..., accum_steps=k)`: a keyword-only option taken here, so that KDStep.__init__ keeps the argument list callers
-    and tests/test_gpu_region_loss.py pin, name for name.  None (the default) takes the optimiser's value."""
+    """`KDStep(..., accum_steps=k, feature_loss=spec)`: keyword-only options taken here, so that KDStep.__init__ keeps the argument
+    list callers and tests/test_gpu_region_loss.py pin, name for name.  accum_steps None (the default) takes the optimiser's value.
+    feature_loss (kdrt.losses.ChannelKD): channel-wise distillation of the two feature maps in the feature MSE's place; None (the
+    default) keeps the MSE and the calls it makes.  A mean over images: with equal shards the reducer's averaged gradient is the
+    global batch's.  beta needs re-tuning when switching (see ChannelKD)."""
 
-    def __call__(cls, *args, accum_steps=None, **kw):
+    def __call__(cls, *args, accum_steps=None, feature_loss=None, **kw):
+        if feature_loss is not None and not isinstance(feature_loss, ChannelKD):
+            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD or None, got {type(feature_loss).__name__}")
         step = super().__call__(*args, **kw)
+        step.feature_loss = feature_loss
         step.cycle = AccumCycle(step.opt, step.reducer, accum_steps)
         return step
 
@@ -74,8 +80,8 @@ class KDStep(metaclass=_TakesAccumSteps):
         """Loss values + the student's backward pass -> (total, parts of detached device scalars)."""
         a = (zs, ms, zt, mt, labels, self.cw, self.T, self.alpha, self.beta, self.ignore_index)
         if self.fused_objective:
-            return kd_objective_backward(*a, hard_loss=self.hard_loss)
-        total, parts = kd_objective(*a, hard_loss=self.hard_loss)
+            return kd_objective_backward(*a, feature_loss=self.feature_loss, hard_loss=self.hard_loss)
+        total, parts = kd_objective(*a, feature_loss=self.feature_loss, hard_loss=self.hard_loss)
         gradsink.drop_pending()
         total.backward()
         if gradsink.pending():

@@ -7,6 +7,9 @@
   lovasz_seg_loss : the opt-in Lovasz-Softmax term (LovaszLoss) added to the weighted CE or to a RegionLoss: the base call, then
                   csrc/kd_loss_lovasz.hip on the same stream, adding its value and its gradient to what the base call wrote
   feature_mse   : F.mse_loss forward + gradient
+  channel_kd    : the opt-in channel-wise distillation feature term (ChannelKD; Shu et al., ICCV 2021) in the feature MSE's place:
+                  a temperature softmax down the H*W positions of every channel of every image, KL to the teacher's
+                  (csrc/kd_loss_cwd.hip; definition in DESIGN.md section 3)
   kd_objective  : CE + alpha*T^2*KL + beta*(MSE(cam) + MSE(lidar))   (the
                   reference has no KD code -- this definition is the build's specification)
   kd_objective_backward : the same objective AND its backward pass for the training step: every loss kernel
@@ -325,15 +328,100 @@ def feature_mse(student_feat, teacher_feat):
     return _MSEFn.apply(student_feat, teacher_feat)
 
 
+@dataclass(frozen=True)
+class ChannelKD:
+    """Channel-wise distillation (Shu et al., ICCV 2021) as the feature term of the KD objective, in the
+    feature MSE's place:
+
+      phi(X)[b,c,i] = exp(X[b,c,i]/tau) / sum_j exp(X[b,c,j]/tau)         i, j over the H*W positions of image b, channel c
+      CWD(S, T)     = tau^2 / (B*C) * sum_{b,c} sum_i phi(T) (log phi(T) - log phi(S)),    dCWD/dS = tau / (B*C) * (phi(S) - phi(T))
+
+    It matches WHERE a channel fires, not how strongly: no adapter, no parameter, same channel count on both sides (a multiple of
+    4 up to 512).  beta keeps its meaning, but the term's magnitude is not the MSE's: re-tune beta when switching.
+    The term is a mean over images: with equal shards under data parallelism the mean of the per-rank values IS the value of the
+    global batch and the reducer's averaged gradient its gradient."""
+    tau: float = 4.0
+
+    def __post_init__(self):
+        t = self.tau
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or t <= 0:
+            raise ValueError(f"ChannelKD: tau must be a finite number > 0, got {t!r}")
+
+
+CWD_MAX_C = 512           # csrc/kd_loss_cwd.hip: a thread owns 4 channels, a workgroup of 256 threads at least 2 rows
+
+
+def _check_feature_spec(spec):
+    if not isinstance(spec, ChannelKD):
+        raise KDError(f"the feature loss must be a kdrt.losses.ChannelKD (or None for the feature MSE), got {type(spec).__name__}")
+
+
+def _check_cwd_pair(a, b):
+    """the kernel indexes both maps as [B*H*W, C] of the student's shape"""
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise KDError(f"channel_kd: student map {tuple(a.shape)} on {a.device} and teacher map {tuple(b.shape)} on {b.device} must be "
+                      "[B, C, H, W] of one shape on one device")
+    C = a.shape[1]
+    if C % 4 != 0 or C > CWD_MAX_C or C < 4:
+        raise KDError(f"channel_kd: {C} channels unsupported (a multiple of 4 up to {CWD_MAX_C})")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise KDError(f"channel_kd: fp32 maps expected, got {a.dtype} and {b.dtype}")
+
+
+def _cwd_call(am, bm, geom, tau, gcoef, gdev, val, ds):
+    """one kd_feat_cwd_fwd_bwd call on the NHWC matrices am, bm [B*H*W, C]: val[0] = CWD, ds = gcoef * gdev[0] * (phi(s) - phi(t))"""
+    B, H, W = geom
+    C = am.shape[1]
+    nbytes = lib.kd_feat_cwd_ws_bytes(B, H * W, C)
+    ws = ops.workspace(nbytes, am.device)
+    lib.call("kd_feat_cwd_fwd_bwd", P(am), P(bm), B, H * W, C, float(tau), float(gcoef), P(gdev), P(val), P(ds), None, P(ws), nbytes, stream())
+
+
+class _ChannelKDFn(torch.autograd.Function):
+    """_MSEFn's shape: forward the value only; backward one more call with the upstream gradient read from device memory, so the
+    gradient coefficient is k = fl32(fl32(tau / (B*C)) * g) -- with g = fl32(beta) from the objective's autograd graph the product
+    kd_objective_backward folds into gcoef on the host."""
+
+    @staticmethod
+    def forward(ctx, a, b, tau):
+        _check_cwd_pair(a, b)
+        ops.require_gpu_tensor(a, "channel_kd")
+        am, geom = ops.nhwc_view(a.detach())
+        bm, _ = ops.nhwc_view(b.detach())
+        val = torch.empty(1, device=a.device, dtype=torch.float32)
+        _cwd_call(am, bm, geom, tau, 0.0, None, val, None)
+        ctx.am, ctx.bm, ctx.geom, ctx.tau = am, bm, geom, tau
+        return val[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        am, bm, geom, tau = ctx.am, ctx.bm, ctx.geom, ctx.tau
+        ds = torch.empty_like(am)
+        val = torch.empty(1, device=am.device, dtype=torch.float32)
+        _cwd_call(am, bm, geom, tau, tau / (geom[0] * am.shape[1]), g.contiguous().view(1), val, ds)
+        return ops.nchw_from_matrix(ds, geom), None, None
+
+
+def channel_kd(student_feat, teacher_feat, tau: float = 4.0):
+    """CWD(student_feat, teacher_feat; tau) of two [B, C, H, W] fp32 maps (see ChannelKD): a device scalar whose gradient flows to
+    the student map only.  KDError on a shape or device mismatch and on a channel count that is no multiple of 4 or above 512."""
+    tau = ChannelKD(tau).tau
+    return _ChannelKDFn.apply(student_feat, teacher_feat, float(tau))
+
+
 def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
                  class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
-                 hard_loss=None):
+                 feature_loss=None, hard_loss=None):
     """total = CE + alpha*T^2*KL + beta*(MSE(camera_feat) + MSE(lidar_feat)); returns (total, parts).
     hard_loss (a RegionLoss): wf*Focal + wt*Tversky takes the CE's place; parts["ce"] then carries it and parts gains "focal"
     and "tversky".  Under data parallelism the Tversky sums cover this rank's shard (see RegionLoss).
     hard_loss (a LovaszLoss): weight * Lovasz is added to its base term (the CE or a RegionLoss); parts["ce"] carries the sum and
-    parts gains "lovasz" and "class_lovasz" (and the base's "focal" / "tversky").  A mean over images: exact under data parallelism."""
+    parts gains "lovasz" and "class_lovasz" (and the base's "focal" / "tversky").  A mean over images: exact under data parallelism.
+    feature_loss (a ChannelKD): beta * (CWD(camera_feat) + CWD(lidar_feat)) at its tau takes the two MSEs' place and parts carries
+    "cwd_cam" / "cwd_lidar" instead of "mse_cam" / "mse_lidar".  A mean over images as well.  beta needs re-tuning (see ChannelKD)."""
     extra = {}
+    if feature_loss is not None:
+        _check_feature_spec(feature_loss)
     if hard_loss is None:
         ce, kl = seg_loss(student_logits, target, class_weights, ignore_index, teacher_logits, T, alpha)
     elif isinstance(hard_loss, LovaszLoss):
@@ -341,20 +429,30 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
     else:
         ce, kl, rp = region_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
         extra = {"focal": rp["focal"], "tversky": rp["tversky"]}
-    mse_c = feature_mse(student_mids["camera_feat"], teacher_mids["camera_feat"])
-    mse_l = feature_mse(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
+    if feature_loss is None:
+        names = ("mse_cam", "mse_lidar")
+        mse_c = feature_mse(student_mids["camera_feat"], teacher_mids["camera_feat"])
+        mse_l = feature_mse(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
+    else:
+        names = ("cwd_cam", "cwd_lidar")
+        mse_c = channel_kd(student_mids["camera_feat"], teacher_mids["camera_feat"], feature_loss.tau)
+        mse_l = channel_kd(student_mids["lidar_feat"], teacher_mids["lidar_feat"], feature_loss.tau)
     # `ce` carries the CE+KL gradient; add KL's value without a second gradient path
     total = ce + (alpha * T * T) * kl.detach() + beta * (mse_c + mse_l)
-    return total, {"ce": ce.detach(), "kl": kl.detach(), "mse_cam": mse_c.detach(), "mse_lidar": mse_l.detach(), **extra}
+    return total, {"ce": ce.detach(), "kl": kl.detach(), names[0]: mse_c.detach(), names[1]: mse_l.detach(), **extra}
 
 
 def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
                           class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
-                          hard_loss=None):
+                          feature_loss=None, hard_loss=None):
     """kd_objective(...)[0].backward() in one: returns (total, parts) with the student's gradients already propagated.
     hard_loss as in kd_objective: the region-loss call writes dL/dlogits together with L_hard / KL in the CE call's place; the
     Lovasz call follows its base call on the same stream and adds its value and its gradient to what that call wrote, before the
     final kernel reads the hard-label term (parts gains "lovasz"; "class_lovasz" comes from the autograd form only).
+    feature_loss (a ChannelKD): each map gets ONE kd_feat_cwd_fwd_bwd call that writes the value and the gradient, with
+    gcoef = fl32(fl32(tau / (B*C)) * fl32(beta)) -- the product the autograd form's backward call forms on the device from its
+    gcoef fl32(tau / (B*C)) and the upstream gradient fl32(beta), so both forms store the same gradient bits; the gradient is
+    deposited exactly as the MSE's is, and kd_kd_total forms the total from the two values ("cwd_cam" / "cwd_lidar").
 
     Same values and the same gradient bits as the autograd formulation, fewer passes: the segmentation-loss call writes
     dL/dlogits together with CE / KL; each feature MSE writes its gradient in the pass that sums its value, and that
@@ -396,6 +494,27 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
         extra = {"focal": hard[3], "tversky": hard[4]}
     roots, grads = [zs], [dzs]
     gradsink.drop_pending()
+    if feature_loss is not None:
+        _check_feature_spec(feature_loss)
+        tau = float(feature_loss.tau)
+        for i, key in enumerate(("camera_feat", "lidar_feat")):
+            a, b = student_mids[key], teacher_mids[key]
+            _check_cwd_pair(a, b)
+            am, geom = ops.nhwc_view(a.detach())
+            bm, _ = ops.nhwc_view(b.detach())
+            want = beta != 0.0 and a.requires_grad
+            da = torch.empty_like(am) if want else None
+            gcoef = float(np.float32(tau / (geom[0] * am.shape[1])) * np.float32(beta))     # the product the autograd form's backward forms
+            _cwd_call(am, bm, geom, tau, gcoef, None, vals[4 + i:5 + i], da)
+            if want:
+                gradsink.deposit(am, da)
+        lib.call("kd_kd_total", P(hard), P(vals[4:5]), P(vals[5:6]), float(alpha * T * T), float(beta), P(vals[6:7]), stream())
+        torch.autograd.backward(roots, grads)
+        if gradsink.pending():
+            gradsink.drop_pending()
+            raise KDError("kd_objective_backward: a feature-map gradient was not collected by the fusion block's backward "
+                          "(unsupported model structure for the fused objective; use kd_objective(...).backward())")
+        return vals[6], {"ce": hard[0], "kl": hard[1], "cwd_cam": vals[4], "cwd_lidar": vals[5], **extra}
     slabs, counts = [], []
     for key in ("camera_feat", "lidar_feat"):
         a, b = student_mids[key], teacher_mids[key]

@@ -22,7 +22,7 @@ import torch.optim as optim
 from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
-from kdrt.losses import LovaszLoss, RegionLoss, confusion, lovasz_seg_loss, region_seg_loss, seg_loss
+from kdrt.losses import ChannelKD, LovaszLoss, RegionLoss, confusion, lovasz_seg_loss, region_seg_loss, seg_loss
 from kdrt.optim import AccumCycle, FusedAdamW, check_accum_steps, decay_groups
 
 try:
@@ -347,16 +347,20 @@ class Trainer:
 
 class KDTrainer(Trainer):
     """Teacher -> student distillation on top of `Trainer`.  total = CE + alpha*T^2*KL + beta*(MSE(camera_feat)
-    + MSE(lidar_feat)) (`hard_loss=RegionLoss(...)`: focal + Tversky in the CE's place); the teacher runs in eval mode under no_grad.  With torch.distributed initialised the
+    + MSE(lidar_feat)) (`hard_loss=RegionLoss(...)`: focal + Tversky in the CE's place; `feature_loss=ChannelKD(tau)`: channel-wise
+    distillation of the two feature maps in the MSEs' place, training only -- validation reports the hard-label loss -- and beta
+    needs re-tuning); the teacher runs in eval mode under no_grad.  With torch.distributed initialised the
     student is broadcast from rank 0 and gradients are all-reduced in buckets overlapped with backward."""
 
-    def __init__(self, model, teacher, train_loader, val_loader, device, T=4.0, alpha=1.0, beta=1.0, **kw):
+    def __init__(self, model, teacher, train_loader, val_loader, device, T=4.0, alpha=1.0, beta=1.0, feature_loss=None, **kw):
+        if feature_loss is not None and not isinstance(feature_loss, ChannelKD):
+            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD or None, got {type(feature_loss).__name__}")
         super().__init__(model, train_loader, val_loader, device, **kw)
         self.teacher = teacher
         if distributed():
             broadcast_module(teacher)           # (a teacher loaded from the same checkpoint on every rank: a no-op in value)
         self.kd_step = KDStep(model, teacher, self.optimizer, self.class_weights, T, alpha, beta, self.ignore_index, self.reducer,
-                              hard_loss=self.hard_loss)
+                              hard_loss=self.hard_loss, feature_loss=feature_loss)
         self.sink = self.kd_step.sink
         self.cycle = self.kd_step.cycle         # one cycle: the KD step's (flush() goes to it)
 

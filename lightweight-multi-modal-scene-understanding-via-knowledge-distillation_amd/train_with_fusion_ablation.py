@@ -13,6 +13,10 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
                  `ce_lovasz`: the weighted cross-entropy + KD_LOVASZ_WEIGHT (1.0) * Lovasz-Softmax (kdrt.losses.LovaszLoss: the
                  direct surrogate of the Jaccard index, per image over the classes present; label maps of at most 128 x 128).
                  `focal_tversky_lovasz`: the same term on top of the RegionLoss the three knobs above describe
+  KD_FEATURE_LOSS   with KD_TEACHER: unset or `mse`: the feature MSE between the student's and the teacher's camera_feat / lidar_feat
+                 maps.  `cwd`: channel-wise distillation in its place (kdrt.losses.ChannelKD: a temperature softmax over the
+                 positions of every channel, KL to the teacher's) at temperature KD_CWD_TAU (4.0); beta keeps its meaning but
+                 the term's magnitude differs from the MSE's, so re-tune it
   KD_EMA_DECAY   unset: off.  e.g. 0.999: keep an EMA of the weights inside the AdamW step; validation, best.pth and the
                  checkpoint's "ema_state" use it.  KD_EMA_WARMUP=1: d_t = min(decay, (1 + t) / (10 + t)).
                  KD_EMA_VALIDATE_LIVE=1 also validates the live weights (history "val_miou_live")
@@ -75,6 +79,17 @@ def hard_loss_from_env(env=os.environ):
     return LovaszLoss(weight=float(env.get("KD_LOVASZ_WEIGHT", 1.0)), base=region)
 
 
+def feature_loss_from_env(env=os.environ):
+    """KD_FEATURE_LOSS -> None (unset or `mse`: the feature MSE) or ChannelKD(tau=KD_CWD_TAU, default 4.0) for `cwd`"""
+    name = env.get("KD_FEATURE_LOSS", "")
+    if name in ("", "mse"):
+        return None
+    if name != "cwd":
+        raise ValueError(f"KD_FEATURE_LOSS must be unset, 'mse' or 'cwd', got {name!r}")
+    from kdrt.losses import ChannelKD
+    return ChannelKD(tau=float(env.get("KD_CWD_TAU", 4.0)))
+
+
 def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, val_scenes, device):
     log(f"\n{'='*80}\nTRAINING: {fusion_type.upper()} FUSION\n{'='*80}")
     train_loader, val_loader = create_pandaset_dataloaders(
@@ -97,7 +112,10 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
     if teacher_ckpt:
         teacher = build_model("concat", 256, device)
         teacher.load_state_dict(torch.load(teacher_ckpt, map_location=device)["model_state"])
-        trainer = KDTrainer(model, teacher, train_loader, val_loader, device, **kw)
+        feature_loss = feature_loss_from_env()
+        if feature_loss is not None:
+            log(f"  Feature loss: {feature_loss} (KD_FEATURE_LOSS / KD_CWD_TAU)")
+        trainer = KDTrainer(model, teacher, train_loader, val_loader, device, feature_loss=feature_loss, **kw)
     else:
         trainer = Trainer(model, train_loader, val_loader, device, **kw)
     best_miou = trainer.train()
