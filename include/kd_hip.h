@@ -355,8 +355,14 @@ size_t kd_weighted_fuse_bwd_ws_bytes(int64_t M, int C);
 int kd_weighted_fuse_bwd(const float* dout, const float* cat, const float* sc, const float* sh, const float* hraw,
                          const float* w2, const float* wts, float* dcat, float* gh, float* dparams, int64_t M,
                          int C, void* ws, size_t ws_bytes, void* stream);
+/* Classifier 1x1 conv (Cin a multiple of 4 up to 64; 1 <= NC <= 16 classes, else KD_ERR_SHAPE) over a deferred NHWC input, NCHW
+ * logits.  The kernels are compiled per class bucket (4, 8, 16) and the call takes the smallest bucket that holds NC; every
+ * per-class operation runs in ascending class order in every bucket.  Backward: gx [M, Cin], partial = the fused BatchNorm-backward
+ * sums (kd_cls_conv_bwd_stat_rows(M, Cin) rows of 2 * Cin), dwb = dW [NC*Cin] | db [NC] with db padded by zeros to a multiple of
+ * 4: kd_cls_conv_dwb_floats(Cin, NC) floats (NC <= 4: NC*Cin + 4), which is also the row of the workspace. */
 int kd_cls_conv_fwd(const float* x, const float* sc, const float* sh, int act, const float* w, const float* b,
                     float* logits_nchw, int64_t M, int HW, int Cin, int NC, void* stream);
+int64_t kd_cls_conv_dwb_floats(int Cin, int NC);
 size_t kd_cls_conv_bwd_ws_bytes(int64_t M, int Cin, int NC);
 int64_t kd_cls_conv_bwd_stat_rows(int64_t M, int Cin);
 int kd_cls_conv_bwd(const float* dlog_nchw, const float* x, const float* sc, const float* sh, int act,
@@ -393,6 +399,9 @@ int kd_bev_rasterize(const float* x, const float* y, const int64_t* cls, const i
                      int remap, uint64_t remap_bits, int H, int W, float x_min, float x_span, float x_max, float y_min,
                      float y_span, float y_max, void* ws, size_t ws_bytes, int64_t* mask, void* stream);
 int kd_semantic_remap(const int64_t* raw, int64_t n, uint64_t remap_bits, int64_t* out, void* stream);
+/* The multi-class remap: out[i] = table[raw[i]] for 0 <= raw[i] < ntab, else 0 (background); table: device int64 [ntab], ntab >= 1;
+ * raw and out are two buffers.  Followed by kd_bev_rasterize with remap = 0 it gives a BEV mask of class indices. */
+int kd_semantic_remap_table(const int64_t* raw, int64_t n, const int64_t* table, int ntab, int64_t* out, void* stream);
 /* out[max_points,4] = stack(x,y,z,i) zero-padded, or (choice != NULL, n >= max_points) the rows choice[0..max_points) */
 int kd_points_prepare(const float* x, const float* y, const float* z, const float* intensity, const int64_t* choice,
                       int64_t n, int64_t max_points, float* out, void* stream);
@@ -463,6 +472,11 @@ int kd_points_augment_batch(float* x, float* y, float* z, float* intensity, cons
 int kd_image_augment_batch(float* img, const float* params, int B, int H, int W, void* stream);
 
 /* ---- losses, metric, optimiser (trainer.py:18-37,55-56,86-90; KD terms are build-defined) ------ */
+/* Weighted CE with ignore_index + temperature KL to a teacher, value and dL/dzs in one call, 2 <= NC <= 16 classes (else
+ * KD_ERR_SHAPE, nothing written).  losses[0] = CE (weighted mean), [1] = KL (per-pixel mean; 0 if zt NULL), [2] = sum of class
+ * weights over the kept pixels, [3] unused.  dzs (NULL: forward only) = gscale * gscale_dev[0] * d/dzs (CE + alpha*T^2*KL).  The
+ * kernels are compiled per class bucket (4, 8, 16) and the call takes the smallest bucket that holds NC; every per-class operation
+ * runs in ascending class order in every bucket, and NC <= 4 runs the bucket-4 code.  ws = kd_seg_loss_ws_bytes(B * HW) bytes. */
 size_t kd_seg_loss_ws_bytes(int64_t npix);
 int kd_seg_loss_fwd_bwd(const float* zs, const float* zt, const int64_t* target, const float* class_w,
                         int ignore_index, float T, float alpha, float gscale, const float* gscale_dev, float* losses,
@@ -531,6 +545,11 @@ int kd_feat_cwd_fwd_bwd(const float* s, const float* t, int B, int HW, int C, fl
  * and pred may be NULL; target NULL: no counting. */
 int kd_argmax_confusion(const float* logits, const int64_t* target, int ignore_index, uint64_t* conf,
                         int64_t* pred, int B, int NC, int M, int HW, void* stream);
+/* kd_argmax_confusion for 1 <= NC <= 16 classes and a matrix width 1 <= M <= 16 (else KD_ERR_SHAPE, nothing written): the same
+ * arguments, counting rule, ties (the lowest class index wins) and NaN behaviour (a NaN never beats the running maximum); 256 LDS
+ * counters per block, accumulated into conf as 64-bit integers.  kd_argmax_confusion keeps its own limits of 4. */
+int kd_argmax_confusion16(const float* logits, const int64_t* target, int ignore_index, uint64_t* conf,
+                          int64_t* pred, int B, int NC, int M, int HW, void* stream);
 int kd_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                   float eps, float weight_decay, int step, float ginv, void* stream);
 /* hipGraph-replay-safe form: state = device float[4] {lr, step, 1-beta1^step, sqrt(1-beta2^step)}; the call

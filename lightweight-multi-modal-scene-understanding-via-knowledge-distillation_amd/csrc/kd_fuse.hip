@@ -295,22 +295,32 @@ struct ClsArgs {
   const float* w; const float* b;                                   // [NC, Cin], [NC]
   float* logits;                                                    // NCHW [B, NC, HW]
   const float* dlog; const float* mean; const float* invstd;        // bwd
-  float* gx; float* partial; float* wslab;                          // [M,Cin]; [grid][2][Cin]; [grid][NC*Cin+4]
+  float* gx; float* partial; float* wslab;                          // [M,Cin]; [grid][2][Cin]; [grid][NC*Cin + db padded to 4]
   int64_t M; int HW; int Cin; int NC; int groups, slots;
 };
 
+// K: the class bucket (4, 8, 16; the launchers take the smallest that holds NC).  Per-class loops run j = 0 .. K-1 in ascending
+// order, unrolled and guarded by j < NC, so the accumulators stay in registers; the K = 4 instances are the kernels as they were.
+constexpr int CLS_MAXC = 16;
+
+// floats of dwb and of one slab row: dW [NC*Cin] | db [NC] padded to a multiple of 4 (NC <= 4: NC*Cin + 4)
+static inline int cls_dwb_floats(int Cin, int NC) { return NC * Cin + 4 * ((NC + 3) / 4); }
+
+template <int K>
 __global__ __launch_bounds__(256) void cls_fwd_kernel(ClsArgs a) {
-  __shared__ float ws[4 * 64 + 4];
+  __shared__ float ws[K * 64 + 4];
   for (int i = threadIdx.x; i < a.NC * a.Cin; i += 256) ws[i] = a.w[i];
   __syncthreads();
   const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (m >= a.M) return;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  float acc[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) acc[j] = 0.f;
   for (int c = 0; c < a.Cin; c += 4) {
     float4 v = kd_ld4(a.x + m * a.Cin + c);
     if (a.sc) v = kd_affine_act4(v, kd_ld4(a.sc + c), kd_ld4(a.sh + c), a.act);
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < K; ++j)
       if (j < a.NC) {
         const float* wj = ws + j * a.Cin + c;
         acc[j] = fmaf(v.w, wj[3], fmaf(v.z, wj[2], fmaf(v.y, wj[1], fmaf(v.x, wj[0], acc[j]))));
@@ -318,22 +328,26 @@ __global__ __launch_bounds__(256) void cls_fwd_kernel(ClsArgs a) {
   }
   const int64_t b = m / a.HW, hw = m % a.HW;
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+  for (int j = 0; j < K; ++j)
     if (j < a.NC) a.logits[(b * a.NC + j) * a.HW + hw] = acc[j] + (a.b ? a.b[j] : 0.f);
 }
 
+template <int K>
 __global__ __launch_bounds__(256) void cls_bwd_kernel(ClsArgs a) {
+  constexpr int KB = K / 4;                       // bias rows of the bucket, 4 classes each
   __shared__ float red[256 * 4];
-  __shared__ float ws[4 * 64 + 4];
+  __shared__ float ws[K * 64 + 4];
   for (int i = threadIdx.x; i < a.NC * a.Cin; i += 256) ws[i] = a.w[i];
   __syncthreads();
   const int tid = threadIdx.x;
   const int gidx = tid % a.groups, slot = tid / a.groups;
   const bool active = slot < a.slots;
   const int c0 = gidx * 4;
-  float4 s1 = kd_zero4(), s2 = kd_zero4(), dwj[4], dbj = kd_zero4();
+  float4 s1 = kd_zero4(), s2 = kd_zero4(), dwj[K], dbj[KB];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) dwj[j] = kd_zero4();
+  for (int j = 0; j < K; ++j) dwj[j] = kd_zero4();
+#pragma unroll
+  for (int q = 0; q < KB; ++q) dbj[q] = kd_zero4();
   if (active) {
     float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = kd_zero4(), mu = kd_zero4(), inv = kd_zero4();
     if (a.sc) { sc = kd_ld4(a.sc + c0); sh = kd_ld4(a.sh + c0); }
@@ -343,9 +357,11 @@ __global__ __launch_bounds__(256) void cls_bwd_kernel(ClsArgs a) {
       const float4 xr = kd_ld4(a.x + m * a.Cin + c0);
       const float4 xa = a.sc ? kd_affine_act4(xr, sc, sh, a.act) : xr;
       float4 g = kd_zero4();
-      float dl[4] = {0.f, 0.f, 0.f, 0.f};
+      float dl[K];
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < K; ++j) dl[j] = 0.f;
+#pragma unroll
+      for (int j = 0; j < K; ++j)
         if (j < a.NC) {
           dl[j] = a.dlog[(b * a.NC + j) * a.HW + hw];
           const float* wj = ws + j * a.Cin + c0;
@@ -353,7 +369,10 @@ __global__ __launch_bounds__(256) void cls_bwd_kernel(ClsArgs a) {
           dwj[j].x = fmaf(dl[j], xa.x, dwj[j].x); dwj[j].y = fmaf(dl[j], xa.y, dwj[j].y);
           dwj[j].z = fmaf(dl[j], xa.z, dwj[j].z); dwj[j].w = fmaf(dl[j], xa.w, dwj[j].w);
         }
-      if (gidx == 0) { dbj.x += dl[0]; dbj.y += dl[1]; dbj.z += dl[2]; dbj.w += dl[3]; }
+      if (gidx == 0) {
+#pragma unroll
+        for (int q = 0; q < KB; ++q) { dbj[q].x += dl[4 * q]; dbj[q].y += dl[4 * q + 1]; dbj[q].z += dl[4 * q + 2]; dbj[q].w += dl[4 * q + 3]; }
+      }
       if (a.sc) {
         g.x *= kd_act_mask(kd_affine(xr.x, sc.x, sh.x), a.act);
         g.y *= kd_act_mask(kd_affine(xr.y, sc.y, sh.y), a.act);
@@ -366,20 +385,28 @@ __global__ __launch_bounds__(256) void cls_bwd_kernel(ClsArgs a) {
       kd_st4(a.gx + m * a.Cin + c0, g);
     }
   }
-  // block reductions: 2 stat rows, NC weight rows, 1 bias row
-  for (int t = 0; t < 7; ++t) {
-    if (t >= 2 && t < 6 && t - 2 >= a.NC) continue;
-    float4 v = t == 0 ? s1 : t == 1 ? s2 : t < 6 ? dwj[t - 2] : dbj;
+  // block reductions: 2 stat rows, NC weight rows, ceil(NC/4) bias rows (rows of the bucket beyond NC are skipped)
+  const int64_t stride = a.NC * a.Cin + 4 * ((a.NC + 3) / 4);
+  float* out = a.wslab + (int64_t)blockIdx.x * stride;
+#pragma unroll
+  for (int t = 0; t < 2 + K + KB; ++t) {
+    if (t >= 2 && t < 2 + K && t - 2 >= a.NC) continue;
+    if (t >= 2 + K && (t - 2 - K) * 4 >= a.NC) continue;
+    float4 v;                                       // t is a constant after unrolling: no dynamic register index
+    if (t == 0) v = s1;
+    else if (t == 1) v = s2;
+    else if (t < 2 + K) v = dwj[t - 2];
+    else v = dbj[t - 2 - K];
     __syncthreads();
     kd_st4(red + tid * 4, v);
     __syncthreads();
-    const int width = t < 6 ? a.Cin : 4;
+    const int width = t < 2 + K ? a.Cin : 4;
     for (int c = tid; c < width; c += 256) {
       float s = 0.f;
       for (int sl = 0; sl < a.slots; ++sl) s += red[(sl * a.groups + c / 4) * 4 + (c & 3)];
       if (t < 2) { if (a.partial) a.partial[((int64_t)blockIdx.x * 2 + t) * a.Cin + c] = s; }
-      else if (t < 6) a.wslab[(int64_t)blockIdx.x * (a.NC * a.Cin + 4) + (t - 2) * a.Cin + c] = s;
-      else a.wslab[(int64_t)blockIdx.x * (a.NC * a.Cin + 4) + a.NC * a.Cin + c] = s;
+      else if (t < 2 + K) out[(t - 2) * a.Cin + c] = s;
+      else out[a.NC * a.Cin + (t - 2 - K) * 4 + c] = s;
     }
   }
 }
@@ -478,30 +505,42 @@ int kd_weighted_fuse_bwd(const float* dout, const float* cat, const float* sc, c
 int kd_cls_conv_fwd(const float* x, const float* sc, const float* sh, int act, const float* w, const float* b,
                     float* logits_nchw, int64_t M, int HW, int Cin, int NC, void* stream) {
   KD_REQUIRE(x && w && logits_nchw && M > 0 && HW > 0 && M % HW == 0, KD_ERR_ARG, "kd_cls_conv_fwd: bad args");
-  KD_REQUIRE(Cin % 4 == 0 && Cin <= 64 && NC >= 1 && NC <= 4, KD_ERR_SHAPE, "kd_cls_conv_fwd: Cin=%d NC=%d unsupported", Cin, NC);
+  KD_REQUIRE(Cin % 4 == 0 && Cin >= 4 && Cin <= 64 && NC >= 1 && NC <= CLS_MAXC, KD_ERR_SHAPE,
+             "kd_cls_conv_fwd: Cin=%d NC=%d unsupported (Cin a multiple of 4 up to 64, NC 1..16)", Cin, NC);
   ClsArgs a{x, sc, sh, act, w, b, logits_nchw, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, M, HW, Cin, NC, 0, 0};
-  hipLaunchKernelGGL(cls_fwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  const dim3 g((unsigned)((M + 255) / 256)), blk(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (NC <= 4) hipLaunchKernelGGL(cls_fwd_kernel<4>, g, blk, 0, st, a);
+  else if (NC <= 8) hipLaunchKernelGGL(cls_fwd_kernel<8>, g, blk, 0, st, a);
+  else hipLaunchKernelGGL(cls_fwd_kernel<16>, g, blk, 0, st, a);
   return kd_check_launch("kd_cls_conv_fwd");
 }
 
+// floats of dwb (and of one workspace row): dW [NC*Cin] | db [NC] padded with zeros to a multiple of 4
+int64_t kd_cls_conv_dwb_floats(int Cin, int NC) { return cls_dwb_floats(Cin, NC); }
 size_t kd_cls_conv_bwd_ws_bytes(int64_t M, int Cin, int NC) {
-  return (size_t)kd_cg_layout(M, Cin, 1024).grid * (NC * Cin + 4) * sizeof(float);
+  return (size_t)kd_cg_layout(M, Cin, 1024).grid * cls_dwb_floats(Cin, NC) * sizeof(float);
 }
 int64_t kd_cls_conv_bwd_stat_rows(int64_t M, int Cin) { return kd_cg_layout(M, Cin, 1024).grid; }
 
-// gx[M,Cin] = act'(.) * (dlog . W); dwb = dW [NC*Cin] | db [NC] (padded to 4).
+// gx[M,Cin] = act'(.) * (dlog . W); dwb = dW [NC*Cin] | db [NC] (padded with zeros to a multiple of 4).
 int kd_cls_conv_bwd(const float* dlog_nchw, const float* x, const float* sc, const float* sh, int act,
                     const float* mean, const float* invstd, const float* w, float* gx, float* partial, float* dwb,
                     int64_t M, int HW, int Cin, int NC, void* ws, size_t ws_bytes, void* stream) {
-  KD_REQUIRE(dlog_nchw && x && w && gx && dwb && ws && M > 0 && M % HW == 0, KD_ERR_ARG, "kd_cls_conv_bwd: bad args");
-  KD_REQUIRE(Cin % 4 == 0 && Cin <= 64 && NC >= 1 && NC <= 4, KD_ERR_SHAPE, "kd_cls_conv_bwd: Cin=%d NC=%d unsupported", Cin, NC);
+  KD_REQUIRE(dlog_nchw && x && w && gx && dwb && ws && M > 0 && HW > 0 && M % HW == 0, KD_ERR_ARG, "kd_cls_conv_bwd: bad args");
+  KD_REQUIRE(Cin % 4 == 0 && Cin >= 4 && Cin <= 64 && NC >= 1 && NC <= CLS_MAXC, KD_ERR_SHAPE,
+             "kd_cls_conv_bwd: Cin=%d NC=%d unsupported (Cin a multiple of 4 up to 64, NC 1..16)", Cin, NC);
   const KdCgLayout l = kd_cg_layout(M, Cin, 1024);
-  KD_REQUIRE(ws_bytes >= (size_t)l.grid * (NC * Cin + 4) * sizeof(float), KD_ERR_WORKSPACE, "kd_cls_conv_bwd: workspace too small");
+  const int row = cls_dwb_floats(Cin, NC);
+  KD_REQUIRE(ws_bytes >= (size_t)l.grid * row * sizeof(float), KD_ERR_WORKSPACE, "kd_cls_conv_bwd: workspace too small");
   ClsArgs a{x, sc, sh, act, w, nullptr, nullptr, dlog_nchw, mean, invstd, gx, partial, (float*)ws, M, HW, Cin, NC, l.groups, l.slots};
-  hipLaunchKernelGGL(cls_bwd_kernel, dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  hipStream_t st = (hipStream_t)stream;
+  if (NC <= 4) hipLaunchKernelGGL(cls_bwd_kernel<4>, dim3(l.grid), dim3(256), 0, st, a);
+  else if (NC <= 8) hipLaunchKernelGGL(cls_bwd_kernel<8>, dim3(l.grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(cls_bwd_kernel<16>, dim3(l.grid), dim3(256), 0, st, a);
   int rc = kd_check_launch("kd_cls_conv_bwd");
   if (rc) return rc;
-  return kd_slab_reduce_launch((const float*)ws, l.grid, NC * Cin + 4, dwb, (hipStream_t)stream);
+  return kd_slab_reduce_launch((const float*)ws, l.grid, row, dwb, st);
 }
 
 }  // extern "C"

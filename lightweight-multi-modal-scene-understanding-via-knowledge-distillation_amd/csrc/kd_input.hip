@@ -69,6 +69,16 @@ __global__ __launch_bounds__(256) void remap_kernel(const int64_t* __restrict__ 
     out[i] = label_of(raw[i], 1, bits);
 }
 
+// out = table[raw], ids outside 0 .. ntab-1 -> 0 (background)
+__global__ __launch_bounds__(256) void remap_table_kernel(const int64_t* __restrict__ raw, int64_t n,
+                                                          const int64_t* __restrict__ table, int ntab,
+                                                          int64_t* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t id = raw[i];
+    out[i] = (id >= 0 && id < ntab) ? table[id] : 0;
+  }
+}
+
 __global__ __launch_bounds__(256) void points_prepare_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                              const float* __restrict__ z, const float* __restrict__ w,
                                                              const int64_t* __restrict__ choice, int64_t n_take,
@@ -257,6 +267,14 @@ int kd_semantic_remap(const int64_t* raw, int64_t n, uint64_t remap_bits, int64_
   if (n == 0) return KD_OK;
   hipLaunchKernelGGL(remap_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, raw, n, remap_bits, out);
   return kd_check_launch("kd_semantic_remap");
+}
+
+// The multi-class form of kd_semantic_remap: out[i] = table[raw[i]] for 0 <= raw[i] < ntab, else 0 (raw and out: two buffers).
+int kd_semantic_remap_table(const int64_t* raw, int64_t n, const int64_t* table, int ntab, int64_t* out, void* stream) {
+  KD_REQUIRE(n >= 0 && (n == 0 || (raw && out)) && table && ntab >= 1, KD_ERR_ARG, "kd_semantic_remap_table: bad args");
+  if (n == 0) return KD_OK;
+  hipLaunchKernelGGL(remap_table_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, raw, n, table, ntab, out);
+  return kd_check_launch("kd_semantic_remap_table");
 }
 
 int kd_points_prepare(const float* x, const float* y, const float* z, const float* intensity, const int64_t* choice,

@@ -9,7 +9,8 @@
 
 namespace {
 
-constexpr int MAXC = 4;
+constexpr int MAXC = 4;                           // the class bucket of the default path and the width of kd_argmax_confusion
+constexpr int SEG_MAXC = 16;                      // kd_seg_loss_fwd_bwd: class buckets 4, 8, 16 (the launcher takes the smallest that holds NC)
 
 struct SegArgs {
   const float* zs; const float* zt; const int64_t* target; const float* cw;
@@ -18,16 +19,19 @@ struct SegArgs {
   int64_t npix; int HW; int NC;
 };
 
+// K: the class bucket.  Every per-class loop runs j = 0 .. K-1 in ascending order, fully unrolled, guarded by j < NC: the
+// per-pixel arrays stay in registers and the operation order is that of the K = 4 instance for every bucket.
+template <int K>
 __device__ __forceinline__ void softmax_c(const float* z, int NC, float invT, float* p, float* logp) {
   float mx = -INFINITY;
 #pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) mx = fmaxf(mx, z[j] * invT);
+  for (int j = 0; j < K; ++j) if (j < NC) mx = fmaxf(mx, z[j] * invT);
   float s = 0.f;
 #pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) { p[j] = expf(z[j] * invT - mx); s += p[j]; }
+  for (int j = 0; j < K; ++j) if (j < NC) { p[j] = expf(z[j] * invT - mx); s += p[j]; }
   const float ls = logf(s);
 #pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) { logp[j] = z[j] * invT - mx - ls; p[j] = p[j] / s; }
+  for (int j = 0; j < K; ++j) if (j < NC) { logp[j] = z[j] * invT - mx - ls; p[j] = p[j] / s; }
 }
 
 __device__ __forceinline__ void block_sum3(float a, float b, float c, float* out3) {
@@ -39,31 +43,32 @@ __device__ __forceinline__ void block_sum3(float a, float b, float c, float* out
   if (threadIdx.x < 3) out3[threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
 }
 
+template <int K>
 __global__ __launch_bounds__(256) void seg_loss_partial_kernel(SegArgs a) {
   float swn = 0.f, sw = 0.f, skl = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.npix; i += (int64_t)gridDim.x * 256) {
     const int64_t b = i / a.HW, hw = i % a.HW;
-    float z[MAXC], p[MAXC], lp[MAXC];
+    float z[K], p[K], lp[K];
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j) if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw];
+    for (int j = 0; j < K; ++j) if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw];
     const int64_t y = a.target[i];
     if (y != a.ignore_index && y >= 0 && y < a.NC) {
-      softmax_c(z, a.NC, 1.f, p, lp);
+      softmax_c<K>(z, a.NC, 1.f, p, lp);
       float nll = 0.f;
 #pragma unroll
-      for (int j = 0; j < MAXC; ++j) if (j == (int)y) nll = -lp[j];
+      for (int j = 0; j < K; ++j) if (j == (int)y) nll = -lp[j];
       const float w = a.cw ? a.cw[y] : 1.f;
       swn = fmaf(w, nll, swn);
       sw += w;
     }
     if (a.zt) {
-      float zt[MAXC], pt[MAXC], lpt[MAXC];
+      float zt[K], pt[K], lpt[K];
 #pragma unroll
-      for (int j = 0; j < MAXC; ++j) if (j < a.NC) zt[j] = a.zt[(b * a.NC + j) * a.HW + hw];
-      softmax_c(z, a.NC, 1.f / a.T, p, lp);
-      softmax_c(zt, a.NC, 1.f / a.T, pt, lpt);
+      for (int j = 0; j < K; ++j) if (j < a.NC) zt[j] = a.zt[(b * a.NC + j) * a.HW + hw];
+      softmax_c<K>(z, a.NC, 1.f / a.T, p, lp);
+      softmax_c<K>(zt, a.NC, 1.f / a.T, pt, lpt);
 #pragma unroll
-      for (int j = 0; j < MAXC; ++j) if (j < a.NC) skl += pt[j] > 0.f ? pt[j] * (lpt[j] - lp[j]) : 0.f;
+      for (int j = 0; j < K; ++j) if (j < a.NC) skl += pt[j] > 0.f ? pt[j] * (lpt[j] - lp[j]) : 0.f;
     }
   }
   block_sum3(swn, sw, skl, a.slab + (int64_t)blockIdx.x * 4);
@@ -86,33 +91,34 @@ __global__ void seg_loss_final_kernel(const float* slab, int nblk, double npix, 
   }
 }
 
+template <int K>
 __global__ __launch_bounds__(256) void seg_loss_grad_kernel(SegArgs a) {
   const float sumw = a.losses[2];
   const float gs = a.gscale * (a.gdev ? a.gdev[0] : 1.f);      // upstream gradient as a device scalar
   const float klc = a.zt ? gs * a.alpha * a.T / (float)a.npix : 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.npix; i += (int64_t)gridDim.x * 256) {
     const int64_t b = i / a.HW, hw = i % a.HW;
-    float z[MAXC], p[MAXC], lp[MAXC], g[MAXC];
+    float z[K], p[K], lp[K], g[K];
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j) { g[j] = 0.f; if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw]; }
+    for (int j = 0; j < K; ++j) { g[j] = 0.f; if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw]; }
     const int64_t y = a.target[i];
     if (y != a.ignore_index && y >= 0 && y < a.NC) {
-      softmax_c(z, a.NC, 1.f, p, lp);
+      softmax_c<K>(z, a.NC, 1.f, p, lp);
       const float w = (a.cw ? a.cw[y] : 1.f) * gs / sumw;
 #pragma unroll
-      for (int j = 0; j < MAXC; ++j) if (j < a.NC) g[j] = w * (p[j] - (j == (int)y ? 1.f : 0.f));
+      for (int j = 0; j < K; ++j) if (j < a.NC) g[j] = w * (p[j] - (j == (int)y ? 1.f : 0.f));
     }
     if (a.zt) {
-      float zt[MAXC], pt[MAXC], lpt[MAXC];
+      float zt[K], pt[K], lpt[K];
 #pragma unroll
-      for (int j = 0; j < MAXC; ++j) if (j < a.NC) zt[j] = a.zt[(b * a.NC + j) * a.HW + hw];
-      softmax_c(z, a.NC, 1.f / a.T, p, lp);
-      softmax_c(zt, a.NC, 1.f / a.T, pt, lpt);
+      for (int j = 0; j < K; ++j) if (j < a.NC) zt[j] = a.zt[(b * a.NC + j) * a.HW + hw];
+      softmax_c<K>(z, a.NC, 1.f / a.T, p, lp);
+      softmax_c<K>(zt, a.NC, 1.f / a.T, pt, lpt);
 #pragma unroll
-      for (int j = 0; j < MAXC; ++j) if (j < a.NC) g[j] = fmaf(klc, p[j] - pt[j], g[j]);
+      for (int j = 0; j < K; ++j) if (j < a.NC) g[j] = fmaf(klc, p[j] - pt[j], g[j]);
     }
 #pragma unroll
-    for (int j = 0; j < MAXC; ++j) if (j < a.NC) a.dzs[(b * a.NC + j) * a.HW + hw] = g[j];
+    for (int j = 0; j < K; ++j) if (j < a.NC) a.dzs[(b * a.NC + j) * a.HW + hw] = g[j];
   }
 }
 
@@ -197,6 +203,32 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* z, const in
   if (conf && threadIdx.x < M * M && loc[threadIdx.x]) atomicAdd(&conf[threadIdx.x], (unsigned long long)loc[threadIdx.x]);
 }
 
+// confusion_kernel for up to 16 classes and a matrix of up to 16 x 16: one LDS counter per thread of the block.  The argmax
+// loop is confusion_kernel's (first maximum wins; a NaN never beats the running maximum, a NaN in class 0 keeps index 0).
+constexpr int CONF16 = 16;
+
+__global__ __launch_bounds__(256) void confusion16_kernel(const float* z, const int64_t* target, int ignore_index,
+                                                          int64_t npix, int HW, int NC, int M, unsigned long long* conf,
+                                                          int64_t* pred) {
+  __shared__ unsigned int loc[CONF16 * CONF16];
+  loc[threadIdx.x] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / HW, hw = i % HW;
+    int best = 0;
+    float bv = z[(b * NC) * HW + hw];
+    for (int j = 1; j < NC; ++j) {
+      const float v = z[(b * NC + j) * HW + hw];
+      if (v > bv) { bv = v; best = j; }
+    }
+    if (pred) pred[i] = best;
+    const int64_t t = target ? target[i] : ignore_index;
+    if (target && t != ignore_index && t >= 0 && t < M && best < M) atomicAdd(&loc[t * M + best], 1u);
+  }
+  __syncthreads();
+  if (conf && threadIdx.x < M * M && loc[threadIdx.x]) atomicAdd(&conf[threadIdx.x], (unsigned long long)loc[threadIdx.x]);
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                                                     float b1, float b2, float eps, float wd, float bc1, float bc2sqrt,
                                                     float ginv) {
@@ -228,16 +260,23 @@ int kd_seg_loss_fwd_bwd(const float* zs, const float* zt, const int64_t* target,
                         int ignore_index, float T, float alpha, float gscale, const float* gscale_dev, float* losses,
                         float* dzs, int B, int NC, int HW, void* ws, size_t ws_bytes, void* stream) {
   KD_REQUIRE(zs && target && losses && ws && B > 0 && HW > 0, KD_ERR_ARG, "kd_seg_loss_fwd_bwd: bad args");
-  KD_REQUIRE(NC >= 2 && NC <= MAXC, KD_ERR_SHAPE, "kd_seg_loss_fwd_bwd: num_classes=%d unsupported (2..4)", NC);
+  KD_REQUIRE(NC >= 2 && NC <= SEG_MAXC, KD_ERR_SHAPE, "kd_seg_loss_fwd_bwd: num_classes=%d unsupported (2..16)", NC);
   const int64_t npix = (int64_t)B * HW;
   int64_t grid = (npix + 255) / 256;
   if (grid > 1024) grid = 1024;
   KD_REQUIRE(ws_bytes >= (size_t)grid * 4 * sizeof(float), KD_ERR_WORKSPACE, "kd_seg_loss_fwd_bwd: workspace too small");
   SegArgs a{zs, zt, target, class_w, ignore_index, T, alpha, gscale, gscale_dev, (float*)ws, losses, dzs, npix, HW, NC};
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(seg_loss_partial_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+  const dim3 g((unsigned)grid), blk(256);
+  if (NC <= 4) hipLaunchKernelGGL(seg_loss_partial_kernel<4>, g, blk, 0, st, a);
+  else if (NC <= 8) hipLaunchKernelGGL(seg_loss_partial_kernel<8>, g, blk, 0, st, a);
+  else hipLaunchKernelGGL(seg_loss_partial_kernel<16>, g, blk, 0, st, a);
   hipLaunchKernelGGL(seg_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, (int)grid, (double)npix, losses);
-  if (dzs) hipLaunchKernelGGL(seg_loss_grad_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
+  if (dzs) {
+    if (NC <= 4) hipLaunchKernelGGL(seg_loss_grad_kernel<4>, g, blk, 0, st, a);
+    else if (NC <= 8) hipLaunchKernelGGL(seg_loss_grad_kernel<8>, g, blk, 0, st, a);
+    else hipLaunchKernelGGL(seg_loss_grad_kernel<16>, g, blk, 0, st, a);
+  }
   return kd_check_launch("kd_seg_loss_fwd_bwd");
 }
 
@@ -302,6 +341,21 @@ int kd_argmax_confusion(const float* logits, const int64_t* target, int ignore_i
   hipLaunchKernelGGL(confusion_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, logits, target,
                      ignore_index, npix, HW, NC, M, (unsigned long long*)conf, pred);
   return kd_check_launch("kd_argmax_confusion");
+}
+
+// kd_argmax_confusion for 1 <= NC <= 16 classes and a matrix width 1 <= M <= 16: same arguments, same counting rule, same ties
+// (the lowest class index) and the same NaN behaviour; 256 LDS counters per block, int64 accumulation.
+int kd_argmax_confusion16(const float* logits, const int64_t* target, int ignore_index, uint64_t* conf, int64_t* pred,
+                          int B, int NC, int M, int HW, void* stream) {
+  KD_REQUIRE(logits && (conf || pred) && B > 0 && HW > 0, KD_ERR_ARG, "kd_argmax_confusion16: bad args");
+  KD_REQUIRE(NC >= 1 && NC <= CONF16, KD_ERR_SHAPE, "kd_argmax_confusion16: num_classes=%d unsupported (1..16)", NC);
+  KD_REQUIRE(M >= 1 && M <= CONF16, KD_ERR_SHAPE, "kd_argmax_confusion16: confusion matrix width %d unsupported (1..16)", M);
+  const int64_t npix = (int64_t)B * HW;
+  int64_t grid = (npix + 255) / 256;
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(confusion16_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, logits, target,
+                     ignore_index, npix, HW, NC, M, (unsigned long long*)conf, pred);
+  return kd_check_launch("kd_argmax_confusion16");
 }
 
 // One AdamW step over flat buffers; `step` is the 1-based step count; grads are scaled by ginv first

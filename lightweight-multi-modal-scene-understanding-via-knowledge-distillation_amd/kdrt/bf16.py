@@ -94,6 +94,9 @@ def forward_bf16(model, images: torch.Tensor, points: torch.Tensor, return_inter
         raise KDError("bf16 path: needs the multiscale camera encoder + FPN (the training entry points' configuration)")
     if not isinstance(model.head, SameResolutionSegmentationHead):
         raise KDError("bf16 path: only the same-resolution head is supported")
+    if model.head.cls.weight.shape[0] > 4:
+        raise KDError(f"bf16 path: the bf16 classifier (kd_bf16_cls_conv) holds at most 4 classes, got {model.head.cls.weight.shape[0]}; "
+                      "5 to 16 classes run in fp32 (model(images, points), teacher_storage='fp32')")
     img = images.contiguous()
     B, Cin, H, W = img.shape
     dev = img.device

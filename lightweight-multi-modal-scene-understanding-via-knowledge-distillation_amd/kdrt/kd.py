@@ -13,6 +13,7 @@ import torch
 
 from . import gradsink, ops, units
 from .ddp import BucketedAllReduce
+from .lib import KDError
 from .losses import ChannelKD, kd_objective, kd_objective_backward
 from .optim import AccumCycle, FusedAdamW
 
@@ -49,6 +50,12 @@ class KDStep(metaclass=_TakesAccumSteps):
                  fused_objective: bool = True, hard_loss=None):
         if teacher_storage not in ("fp32", "bf16"):
             raise ValueError(f"teacher_storage must be 'fp32' or 'bf16', got {teacher_storage!r}")
+        if teacher_storage == "bf16":
+            cls_conv = getattr(getattr(teacher, "head", None), "cls", None)
+            nc = cls_conv.weight.shape[0] if cls_conv is not None else 0
+            if nc > 4:             # here and not at the first step: the bf16 classifier kernel is the limit
+                raise KDError(f"teacher_storage='bf16': the bf16 classifier (kd_bf16_cls_conv) holds at most 4 classes, the teacher "
+                              f"emits {nc}; 5 to 16 classes need teacher_storage='fp32'")
         # fused objective (default): loss values and loss gradients from the same kernel passes, feature-MSE gradients added
         # inside the fusion block's data-gradient GEMMs (losses.kd_objective_backward); False keeps the
         # autograd formulation kd_objective(...).backward() -- same bits, more passes (tests compare the two)

@@ -1,7 +1,8 @@
 """Loss / metric Functions of the KD step (device-side values, no host sync).
 
   seg_loss      : weighted CE with ignore_index (trainer.py:55,88), optionally + alpha*T^2*KL to a
-                  teacher's logits -- value and dL/dlogits produced by one fused HIP call
+                  teacher's logits -- value and dL/dlogits produced by one fused HIP call; 2 to 16 classes (the opt-in
+                  RegionLoss / LovaszLoss terms below: 2 to 4)
   region_seg_loss : the opt-in hard-label loss wf*Focal + wt*Tversky (RegionLoss) in place of the weighted CE, same fused
                   form (csrc/kd_loss_region.hip; definition in DESIGN.md section 3)
   lovasz_seg_loss : the opt-in Lovasz-Softmax term (LovaszLoss) added to the weighted CE or to a RegionLoss: the base call, then
@@ -145,8 +146,19 @@ def _check_region_spec(spec):
         raise KDError(f"the hard-label loss must be a kdrt.losses.RegionLoss (or None for the weighted CE), got {type(spec).__name__}")
 
 
+HARD_MAX_NC = 4           # RegionLoss and LovaszLoss: per-class slots of REGION_VALS / LOVASZ_VALS and of their kernels
+
+
+def _check_hard_classes(name, NC):
+    """the weighted CE + KL runs 2..16 classes; the region and Lovasz kernels keep their limit of 4"""
+    if NC > HARD_MAX_NC:
+        raise KDError(f"{name}: at most {HARD_MAX_NC} classes, the logits have {NC}; 5 to 16 classes train with the weighted CE "
+                      "(hard_loss=None)")
+
+
 def _region_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, vals, dzs):
     B, NC, H, W = zs.shape
+    _check_hard_classes("RegionLoss", NC)
     nbytes = lib.kd_seg_region_loss_ws_bytes(B * H * W)
     ws = ops.workspace(nbytes, zs.device)
     lib.call("kd_seg_region_loss_fwd_bwd", P(zs), P(zt), P(target), P(class_w), int(ignore_index), float(T), float(alpha),
@@ -228,6 +240,7 @@ LOVASZ_MAX_HW = 16384     # 8-byte keys of one image in the LDS of one CU
 def _lovasz_call(spec, zs, target, ignore_index, gdev, vals, hard, dzs):
     """the Lovasz call that follows the base call on the same stream: hard[0] += weight * L, dzs += weight * gdev[0] * dL/dzs"""
     B, NC, H, W = zs.shape
+    _check_hard_classes("LovaszLoss", NC)
     if H * W > LOVASZ_MAX_HW:
         raise KDError(f"LovaszLoss: a {H} x {W} map has {H * W} pixels per image, the per-image sort holds at most {LOVASZ_MAX_HW} (128 x 128)")
     nbytes = lib.kd_seg_lovasz_ws_bytes(B, NC, H * W)
@@ -239,6 +252,7 @@ def _lovasz_call(spec, zs, target, ignore_index, gdev, vals, hard, dzs):
 def _hard_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, lov, dzs):
     """base call (weighted CE or region loss) into hard / dzs, then the Lovasz call adding to both.  hard: REGION_VALS floats
     ([0] the hard-label term, [1] KL in either layout), lov: LOVASZ_VALS floats."""
+    _check_hard_classes("LovaszLoss", zs.shape[1])                # before the base call writes anything
     if spec.base is None:
         _SegLossFn._call(zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, dzs)
     else:
@@ -543,7 +557,7 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
 
 def confusion(logits, target, num_classes: int = 2, ignore_index: int = -1, out: Optional[torch.Tensor] = None):
     """Accumulates into (or creates) an int64 [M, M] device confusion matrix, M = num_classes; returns (conf, argmax).
-    M need not be the logits' class count: a pixel counts at [t, argmax] when 0 <= t < M and argmax < M (trainer.py:18-26);
+    Up to 16 classes and M <= 16 (KDError beyond).  M need not be the logits' class count: a pixel counts at [t, argmax] when 0 <= t < M and argmax < M (trainer.py:18-26);
     the returned argmax is over all classes."""
     ops.require_gpu_tensor(logits, "confusion")
     z = logits.detach().contiguous()
@@ -558,5 +572,7 @@ def confusion(logits, target, num_classes: int = 2, ignore_index: int = -1, out:
         raise KDError(f"confusion: `out` must be a contiguous int64 [{M}, {M}] tensor on {z.device}, got "
                       f"{tuple(out.shape)} {out.dtype} on {out.device}")
     pred = torch.empty(B, H, W, device=z.device, dtype=torch.int64)
-    lib.call("kd_argmax_confusion", P(z), P(target.contiguous()), int(ignore_index), P(out), P(pred), B, NC, M, H * W, stream())
+    # up to 4 classes and a 4 x 4 matrix: the entry the default path has always called; beyond, the 16-wide one
+    entry = "kd_argmax_confusion" if NC <= 4 and M <= 4 else "kd_argmax_confusion16"
+    lib.call(entry, P(z), P(target.contiguous()), int(ignore_index), P(out), P(pred), B, NC, M, H * W, stream())
     return out, pred

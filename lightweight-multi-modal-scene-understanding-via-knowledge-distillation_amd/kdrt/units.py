@@ -1011,7 +1011,7 @@ class SameHeadFn(torch.autograd.Function):
         gx = torch.empty(M, Cin, device=dev, dtype=torch.float32)
         rows = lib.kd_cls_conv_bwd_stat_rows(M, Cin)
         partial = torch.empty(rows * 2 * Cin, device=dev, dtype=torch.float32)
-        dwb = torch.empty(NC * Cin + 4, device=dev, dtype=torch.float32)
+        dwb = torch.empty(lib.kd_cls_conv_dwb_floats(Cin, NC), device=dev, dtype=torch.float32)   # dW [NC*Cin] | db [NC] padded to 4
         nbytes = lib.kd_cls_conv_bwd_ws_bytes(M, Cin, NC)
         ws = ops.workspace(nbytes, dev)
         lib.call("kd_cls_conv_bwd", P(dlog), P(cur.raw), P(cur.sc), P(cur.sh), cur.act, P(cur.bnc.mean), P(cur.bnc.invstd),
@@ -1033,6 +1033,9 @@ class X4HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, units, training, wc, bc, *params):
+        if wc.shape[0] > 4:                        # before the two upsampling stages run
+            raise KDError(f"output_mode='x4': the 3x3 classifier (kd_cls3x3_*) holds at most 4 classes, got {wc.shape[0]}; "
+                          "5 to 16 classes need output_mode='same'")
         xm, geom = ops.nhwc_view(x)
         cur = Operand(xm, geom)
         recs = []

@@ -96,6 +96,50 @@ def remap_semantic(raw_ids):
     return out.cpu().numpy() if isinstance(raw_ids, np.ndarray) else out
 
 
+MAX_CLASSES = 16          # the widest head the loss, classifier and metric kernels take
+
+
+def class_map_table(class_map) -> np.ndarray:
+    """`class_map` -> the int64 lookup table of kd_semantic_remap_table: table[raw id] = class index, ids the map does not name -> 0.
+    A dict {raw id: class} or a sequence indexed by raw id; raw ids are integers >= 0, classes integers in [0, 15] with 0 the
+    background.  Anything else is a ValueError."""
+    def _int(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"class_map: {what} must be an integer, got {v!r}")
+        return int(v)
+    if isinstance(class_map, dict):
+        items = [(_int(k, "a raw id"), _int(v, "a class index")) for k, v in class_map.items()]
+    elif isinstance(class_map, (list, tuple, np.ndarray)) and np.ndim(class_map) == 1:
+        items = [(i, _int(v, "a class index")) for i, v in enumerate(list(class_map))]
+    else:
+        raise ValueError(f"class_map must be a dict {{raw id: class}} or a sequence indexed by raw id, got {type(class_map).__name__}")
+    if not items:
+        raise ValueError("class_map is empty")
+    for k, v in items:
+        if k < 0 or k >= (1 << 20):
+            raise ValueError(f"class_map: raw id {k} outside [0, 2^20)")
+        if v < 0 or v >= MAX_CLASSES:
+            raise ValueError(f"class_map: class index {v} (raw id {k}) outside [0, {MAX_CLASSES - 1}]")
+    table = np.zeros(max(k for k, _ in items) + 1, np.int64)
+    for k, v in items:
+        table[k] = v
+    return table
+
+
+def remap_semantic_table(raw_ids, table, s: int = None):
+    """raw class ids -> table[raw id] on the device (ids outside the table -> 0): numpy in -> numpy out, tensor in -> CUDA tensor
+    out, like remap_semantic.  `table`: what class_map_table returns, or its CUDA copy; `s`: the stream (default the current one)."""
+    ids = _dev(raw_ids, torch.int64)
+    tab = _dev(table, torch.int64).reshape(-1)
+    if tab.numel() == 0:
+        raise KDError("remap_semantic_table needs a table of at least one entry")
+    flat = ids.reshape(-1)
+    out = torch.empty_like(flat)
+    lib.call("kd_semantic_remap_table", P(flat), flat.numel(), P(tab), tab.numel(), P(out), stream() if s is None else s)
+    out = out.reshape(ids.shape)
+    return out.cpu().numpy() if isinstance(raw_ids, np.ndarray) else out
+
+
 def rasterize_bev(x, y, labels, grid_size: Tuple[int, int] = (64, 64),
                   pc_range: Tuple[float, float, float, float] = (-50, 50, -50, 50)):
     """Per-point labels -> BEV mask, first non-zero label per cell in point order.  numpy in -> numpy out."""
@@ -217,14 +261,17 @@ class StagingSet:
 
 
 class PandaSetDataset(Dataset):
-    """2-class version: background (0) and drivable (1, includes lanes)."""
+    """2-class version: background (0) and drivable (1, includes lanes).  `class_map` (a dict or sequence raw id -> class index
+    in [0, NC-1], 0 = background; see class_map_table): the multi-class version -- every prepare path then runs the table remap as
+    one extra launch and rasterises the class indices (first point in input order with a non-zero class wins, as before)."""
 
     def __init__(self, root: str, scene_ids: List[str], image_size: Tuple[int, int] = (256, 256),
                  grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, verbose: bool = True,
-                 device_resize: bool = False):
+                 device_resize: bool = False, class_map=None):
         self.root, self.scene_ids = root, scene_ids
         self.image_size, self.grid_size, self.max_points = image_size, grid_size, max_points
         self.device_resize = bool(device_resize)
+        self.set_class_map(class_map)
         self.pc_range = (-50, 50, -50, 50)
         self.samples = self._index_scenes(verbose=verbose)
         if verbose:
@@ -252,6 +299,31 @@ class PandaSetDataset(Dataset):
 
     def __len__(self):
         return len(self.samples)
+
+    class_table = _table_dev = None                # a subclass with its own constructor stays 2-class
+
+    def set_class_map(self, class_map):
+        """None: the 2-class drivable remap inside the rasteriser (the default).  Else validated here (ValueError)."""
+        self.class_table = None if class_map is None else class_map_table(class_map)
+        self._table_dev = None
+
+    def __getstate__(self):                        # a pickled copy (spawned DataLoader workers) carries no device tensor
+        return {**self.__dict__, "_table_dev": None}
+
+    @property
+    def num_classes(self) -> int:
+        return 2 if self.class_table is None else int(self.class_table.max()) + 1
+
+    def _labels(self, cls: torch.Tensor, n: int, s: int):
+        """(labels, remap flag) for kd_bev_rasterize on stream `s`: the raw ids and the drivable remap, or -- with a class map --
+        the table-remapped ids (one more launch) and no remap."""
+        if self.class_table is None:
+            return cls, 1
+        if self._table_dev is None:                # copied once, on the first batch (the workers never touch the GPU)
+            self._table_dev = torch.from_numpy(self.class_table).cuda()
+        out = torch.empty_like(cls)
+        lib.call("kd_semantic_remap_table", P(cls), n, P(self._table_dev), self._table_dev.numel(), P(out), s)
+        return out, 0
 
     def load_raw(self, idx: int) -> Dict[str, object]:
         """Host I/O only (safe in DataLoader workers): decoded + resized uint8 image, float32 point columns,
@@ -285,7 +357,16 @@ class PandaSetDataset(Dataset):
             return self._prepare_batch_augmented(raws, augment, frame_keys, sample_seed)
         xs = [_dev(r["x"], torch.float32) for r in raws]
         ys = [_dev(r["y"], torch.float32) for r in raws]
-        seg = rasterize_bev_batch(xs, ys, [r["class"] for r in raws], self.grid_size, self.pc_range, remap=True)
+        if self.class_table is None:
+            seg = rasterize_bev_batch(xs, ys, [r["class"] for r in raws], self.grid_size, self.pc_range, remap=True)
+        else:
+            raw = torch.cat([_dev(r["class"], torch.int64).reshape(-1) for r in raws])
+            if raw.numel() != sum(int(x.numel()) for x in xs):
+                raise KDError("x, y and labels must have the same length per frame")
+            lab, _ = self._labels(raw, raw.numel(), stream())
+            bounds = np.concatenate([[0], np.cumsum([int(x.numel()) for x in xs])]).tolist()
+            seg = rasterize_bev_batch(xs, ys, [lab[a:b] for a, b in zip(bounds[:-1], bounds[1:])], self.grid_size, self.pc_range,
+                                      remap=False)
         pts = torch.stack([prepare_points(x, y, r["z"], r["i"], self.max_points) for x, y, r in zip(xs, ys, raws)])
         img = torch.stack([self._image_chw(r["image_u8"]) for r in raws])
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
@@ -320,7 +401,8 @@ class PandaSetDataset(Dataset):
         seg = torch.empty(B, GH, GW, dtype=torch.int64, device="cuda")
         nbytes = lib.kd_bev_rasterize_ws_bytes(B, GH, GW)
         ws = workspace(nbytes, seg.device)
-        lib.call("kd_bev_rasterize", P(x), P(y), P(cls), P(off), B, n, 1, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
+        lab, remap = self._labels(cls, n, s)
+        lib.call("kd_bev_rasterize", P(x), P(y), P(lab), P(off), B, n, remap, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
                  _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws), nbytes, P(seg), s)
         pts = torch.stack([prepare_points(*(v[a:b] for v in (x, y, z, w)), self.max_points)
                            for a, b in zip(bounds[:-1].tolist(), bounds[1:].tolist())])
@@ -334,7 +416,7 @@ class PandaSetDataset(Dataset):
         """`prepare_batch` for a whole batch at once, enqueued on the stream `side`: one host-to-device copy per tensor
         from the pinned `staging` set (packed point columns, class ids, uint8 images, offsets + frame keys), then three
         launches (rasteriser, batched points, batched images -- with `device_resize` and full-size frames the image
-        launch is the Pillow-exact resize).  Sweeps longer than max_points are cut by the device
+        launch is the Pillow-exact resize; with a class map one more, the table remap ahead of the rasteriser).  Sweeps longer than max_points are cut by the device
         sampler of kd_points_prepare_batch under (`sample_seed`, frame key).  The tensors returned belong to `side`:
         a consumer on another stream waits for an event recorded after this call and tells the allocator
         (`record_stream`).  `ws_holder`: a one-element list that keeps the rasteriser's workspace of this stream.
@@ -381,7 +463,8 @@ class PandaSetDataset(Dataset):
             s = side.cuda_stream
             if augment is not None:
                 _augment_launches(augment, params, x, y, z, w, off, keys, B, n, sample_seed, s)
-            lib.call("kd_bev_rasterize", P(x), P(y), P(cls), P(off), B, n, 1, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
+            lab, remap = self._labels(cls, n, s)
+            lib.call("kd_bev_rasterize", P(x), P(y), P(lab), P(off), B, n, remap, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
                      _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws_holder[0]), nbytes, P(seg), s)
             lib.call("kd_points_prepare_batch", P(x), P(y), P(z), P(w), P(off), P(keys), B, n, self.max_points,
                      int(sample_seed) & 0xFFFFFFFFFFFFFFFF, P(pts), s)
@@ -599,8 +682,14 @@ class DeviceBatchLoader:
 
 
 class SyntheticPandaSet(Dataset):
-    def __init__(self, n_frames=64, num_points=5000, image_size=256, bev_size=64, seed=0, pad_tail=250):
+    """`num_classes` (default 2: the frames as they always were): labels drawn in [0, num_classes - 1], background (0) at the same
+    ~87 % and the other classes sharing the rest evenly."""
+
+    def __init__(self, n_frames=64, num_points=5000, image_size=256, bev_size=64, seed=0, pad_tail=250, num_classes=2):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= MAX_CLASSES:
+            raise ValueError(f"SyntheticPandaSet: num_classes must be an integer in [2, {MAX_CLASSES}], got {num_classes!r}")
         self.n, self.N, self.hw, self.g, self.seed, self.pad = n_frames, num_points, image_size, bev_size, seed, pad_tail
+        self.num_classes = num_classes
 
     def __len__(self):
         return self.n
@@ -614,8 +703,10 @@ class SyntheticPandaSet(Dataset):
         if self.pad:
             pts[self.N - self.pad:] = 0.0
         seg = (torch.rand(self.g, self.g, generator=g) < 0.13).long()        # ~87 % background (real data)
-        return {"image": torch.rand(3, self.hw, self.hw, generator=g), "points": pts, "segmentation": seg,
-                "sample_token": f"synthetic_{i:06d}"}
+        img = torch.rand(3, self.hw, self.hw, generator=g)
+        if self.num_classes > 2:                   # the last draw: image, points and the foreground mask keep their values
+            seg = seg * torch.randint(1, self.num_classes, (self.g, self.g), generator=g)
+        return {"image": img, "points": pts, "segmentation": seg, "sample_token": f"synthetic_{i:06d}"}
 
 
 class SyntheticRawPandaSet(PandaSetDataset):
@@ -629,10 +720,11 @@ class SyntheticRawPandaSet(PandaSetDataset):
 
     def __init__(self, n_frames: int = 64, sweep_points=169000, image_size: Tuple[int, int] = (256, 256),
                  grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, seed: int = 0, nan_frames: Sequence[int] = (),
-                 unique: int = None, source_size: Tuple[int, int] = None, device_resize: bool = False):
+                 unique: int = None, source_size: Tuple[int, int] = None, device_resize: bool = False, class_map=None):
         self.root, self.scene_ids = None, []
         self.image_size, self.grid_size, self.max_points = image_size, grid_size, max_points
         self.source_size, self.device_resize = source_size, bool(device_resize)
+        self.set_class_map(class_map)
         self.pc_range = (-50, 50, -50, 50)
         self.seed, self.nan_frames = seed, set(int(i) for i in nan_frames)
         self.sweeps = [int(sweep_points)] if np.isscalar(sweep_points) else [int(v) for v in sweep_points]
@@ -665,7 +757,7 @@ class SyntheticRawPandaSet(PandaSetDataset):
 
 def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: List[str], batch_size: int = 4,
                                 num_workers: int = 0, verbose: bool = True, to_cpu: bool = None, prefetch: int = None,
-                                device_resize: bool = None, augment=None):
+                                device_resize: bool = None, augment=None, class_map=None):
     """Reference signature (pandaset_dataset.py:144-160) plus `to_cpu`: batches stay on the GPU by default (the trainers'
     `.to(device)` is then free); to_cpu=True (or KD_LOADER_TO_CPU=1) returns host tensors for the reference's analysis
     scripts, which call `.numpy()` on them (test_dataset_distribution.py:22, verify_2class_distribution.py).
@@ -674,7 +766,9 @@ def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: 
     default off): the workers only decode and the bilinear resize runs on the device with Pillow's bytes.  `augment` (an
     `Augment`, or its parse form "rot=5,flip=0.5,..."; None: KD_LOADER_AUGMENT, empty or unset = off): opt-in training
     augmentation on the device, see DeviceBatchLoader; it goes to the TRAINING loader only.  The synthetic fallback serves
-    ready-made tensors and ignores the setting."""
+    ready-made tensors and ignores the setting.  `class_map` (None: the 2-class drivable labels): raw id -> class index for
+    multi-class labels, see PandaSetDataset (ValueError if malformed); the synthetic fallback then draws labels in the map's
+    range of classes."""
     if to_cpu is None:
         to_cpu = os.environ.get("KD_LOADER_TO_CPU") == "1"
     if prefetch is None:
@@ -684,12 +778,13 @@ def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: 
     if augment is None:
         augment = os.environ.get("KD_LOADER_AUGMENT", "")
     augment = as_augment(augment)
+    table = None if class_map is None else class_map_table(class_map)
     pf = {"prefetch": prefetch, "sample_seed": int(os.environ.get("KD_LOADER_SAMPLE_SEED", "0"))}
     # under torch.distributed (one process per GPU) the FRAMES are sharded over ranks, equal counts per rank for training
     rank, world = _dist_rank_world()
     if os.path.isdir(root):
-        train_ds = PandaSetDataset(root, train_scenes, verbose=verbose, device_resize=device_resize)
-        val_ds = PandaSetDataset(root, val_scenes, verbose=verbose, device_resize=device_resize)
+        train_ds = PandaSetDataset(root, train_scenes, verbose=verbose, device_resize=device_resize, class_map=class_map)
+        val_ds = PandaSetDataset(root, val_scenes, verbose=verbose, device_resize=device_resize, class_map=class_map)
         return (DeviceBatchLoader(train_ds, batch_size, shuffle=True, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world,
                                   augment=augment, **pf),
                 DeviceBatchLoader(val_ds, batch_size, shuffle=False, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf))
@@ -697,8 +792,9 @@ def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: 
         print(f"[data] '{root}' not found: serving synthetic PandaSet-shaped frames")
         if augment is not None:
             print("[data] the synthetic frames are ready-made tensors: the augment setting is ignored")
-    train = SyntheticPandaSet(n_frames=max(8, 8 * len(train_scenes)), seed=1)
-    val = SyntheticPandaSet(n_frames=max(4, 4 * len(val_scenes)), seed=2)
+    nc = {} if table is None else {"num_classes": max(2, int(table.max()) + 1)}
+    train = SyntheticPandaSet(n_frames=max(8, 8 * len(train_scenes)), seed=1, **nc)
+    val = SyntheticPandaSet(n_frames=max(4, 4 * len(val_scenes)), seed=2, **nc)
     if world > 1:
         ts = RankShardSampler(len(train), rank, world, shuffle=True, equal=True)
         vs = RankShardSampler(len(val), rank, world, shuffle=False, equal=False)

@@ -22,6 +22,7 @@ import torch.optim as optim
 from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
+from kdrt.lib import KDError
 from kdrt.losses import ChannelKD, LovaszLoss, RegionLoss, confusion, lovasz_seg_loss, region_seg_loss, seg_loss
 from kdrt.optim import AccumCycle, FusedAdamW, check_accum_steps, decay_groups
 
@@ -108,7 +109,20 @@ class SegmentationMetrics:
         return {"class_iou": ious, "miou": float(np.mean(ious))}
 
 
-class Trainer:
+class _TakesNumClasses(type):
+    """`Trainer(..., num_classes=n)` / `KDTrainer(..., num_classes=n)`: a keyword-only option taken here, so that Trainer.__init__
+    keeps the argument list the tests pin, name for name (as KDStep does for accum_steps and feature_loss).  None (the default)
+    changes nothing."""
+
+    def __call__(cls, *args, num_classes=None, **kw):
+        if num_classes is not None and (isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= 16):
+            raise ValueError(f"num_classes must be an integer in [2, 16] or None, got {num_classes!r}")
+        trainer = super().__call__(*args, **kw)
+        trainer.set_num_classes(num_classes)
+        return trainer
+
+
+class Trainer(metaclass=_TakesNumClasses):
     def __init__(self, model, train_loader, val_loader, device, lr=1e-3, weight_decay=1e-3, save_dir="checkpoints",
                  class_weights=None, num_epochs=20, accum_steps=1, max_grad_norm=None, ema_decay=None, ema_warmup=False,
                  no_decay_norm_bias=False, lr_mult=None, hard_loss=None):
@@ -121,6 +135,8 @@ class Trainer:
             class_weights = torch.FloatTensor(class_weights).to(device)
         self.class_weights = class_weights
         self.ignore_index = -1
+        self.num_classes, self.metric_classes = None, 2        # `num_classes=` is taken by _TakesNumClasses, see set_num_classes
+        self.train_confusion = self.val_confusion = None       # the confusion matrices of the last train_epoch() / validation pass
         # hard_loss (kdrt.losses.RegionLoss): train AND validate with wf*Focal + wt*Tversky instead of the weighted CE (the class
         # weights then enter the focal term only).  Data parallel: the Tversky sums cover each rank's own shard of the batch.
         # hard_loss (kdrt.losses.LovaszLoss): its base term (the weighted CE or a RegionLoss) + weight * Lovasz-Softmax, a mean over
@@ -187,6 +203,19 @@ class Trainer:
             self.history["val_miou_live"] = []
         self.last_val_miou_live = None
 
+    def set_num_classes(self, num_classes):
+        """num_classes (None, the default: the reference's 2-class metrics on whatever the head emits): the width of the confusion
+        matrix of training and validation, 2 to 16; it must agree with the length of class_weights.  The head's own class count
+        is the model's (CompleteSegmentationModel(num_classes=...)); more than 4 classes need the same-resolution head, the weighted
+        CE (hard_loss=None) and, for KD, an fp32 teacher."""
+        if num_classes is not None:
+            if self.class_weights is not None and self.class_weights.numel() != num_classes:
+                raise ValueError(f"class_weights has {self.class_weights.numel()} entries for num_classes={num_classes}")
+            if self.hard_loss is not None and num_classes > 4:
+                raise KDError(f"hard_loss (RegionLoss / LovaszLoss) holds at most 4 classes, num_classes={num_classes}")
+        self.num_classes = num_classes
+        self.metric_classes = 2 if num_classes is None else num_classes
+
     def _log(self, *a, **k):
         """Console output of the training loop: rank 0 only under data parallelism (errors and warnings of the other
         ranks still reach their own stderr -- nothing is patched process-wide)."""
@@ -226,7 +255,7 @@ class Trainer:
 
     def train_epoch(self):
         self.model.train()
-        metrics = SegmentationMetrics(num_classes=2, device=self.device)
+        metrics = SegmentationMetrics(num_classes=self.metric_classes, device=self.device)
         total = torch.zeros((), device=self.device)
         gnorm = torch.zeros((), device=self.device) if self.max_grad_norm is not None else None
         steps = 0
@@ -248,7 +277,9 @@ class Trainer:
         if gnorm is not None:                  # identical on every rank: no mean over ranks (a skipped step's inf / NaN shows here)
             # the mean over optimiser steps (without accumulation: one per loader batch, the divisor as it was)
             self.last_epoch_grad_norm = gnorm.item() / max(steps if self.accum_steps > 1 else len(self.train_loader), 1)
-        return self._mean_over_ranks(total, len(self.train_loader)), metrics.compute()
+        out = metrics.compute()
+        self.train_confusion = metrics.confusion.copy()      # int64 [metric_classes, metric_classes], summed over ranks
+        return self._mean_over_ranks(total, len(self.train_loader)), out
 
     def validate(self):
         if self.ema_decay is None:
@@ -262,7 +293,7 @@ class Trainer:
         self.model.eval()
         if distributed():
             broadcast_buffers(self.model)       # all ranks evaluate rank 0's BatchNorm statistics (the model that is saved)
-        metrics = SegmentationMetrics(num_classes=2, device=self.device)
+        metrics = SegmentationMetrics(num_classes=self.metric_classes, device=self.device)
         total = torch.zeros((), device=self.device)
         with torch.no_grad():
             for batch in tqdm(self.val_loader, desc="Val", disable=not self.is_main):
@@ -272,7 +303,9 @@ class Trainer:
                 logits = self.model(imgs, pts)
                 total += self.criterion(logits, seg)
                 metrics.update(logits, seg)
-        return self._mean_over_ranks(total, len(self.val_loader)), metrics.compute()
+        out = metrics.compute()
+        self.val_confusion = metrics.confusion.copy()
+        return self._mean_over_ranks(total, len(self.val_loader)), out
 
     def save_checkpoint(self, epoch, val_miou, is_best=False):
         if not self.is_main:
@@ -331,7 +364,8 @@ class Trainer:
             self._log(f"  Val Loss:   {val_loss:.4f} | Val mIoU:   {val_miou:.4f}")
             self._log(f"  Learning Rate: {current_lr:.6f}")
             self._log("\n  Per-class IoU (Val):")
-            for name, iou in zip(["Background", "Drivable"], val_metrics["class_iou"]):
+            names = ["Background", "Drivable"] if self.num_classes is None else ["Background"] + [f"Class {i}" for i in range(1, self.num_classes)]
+            for name, iou in zip(names, val_metrics["class_iou"]):
                 self._log(f"    {name:12s}: {iou:.4f}")
             self.update_history(train_loss, train_miou, val_loss, val_miou, current_lr)
             is_best = val_miou > self.best_miou

@@ -24,6 +24,11 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
   KD_LR_MULT     "camera_encoder=0.1,...": learning-rate multiplier per top-level module of the model
   KD_ACCUM_STEPS unset: 1.  k: gradient accumulation, one optimiser step per k loader batches on the mean of their gradients
                  (BatchNorm statistics per batch; data parallel: one set of all-reduces per optimiser step, not per batch)
+  KD_NUM_CLASSES / KD_CLASS_MAP   both unset: the 2-class drivable-area task.  KD_NUM_CLASSES=n (2..16): the head emits n classes,
+                 the metrics are n wide and the class weights are 0.4 for the background and 3.5 for every other class.
+                 KD_CLASS_MAP: the path of a JSON file {"raw id": class, ...} from PandaSet's raw semantic ids to class indices
+                 in [0, n-1] (0 = background; ids it does not name are background); alone it sets n to the largest class + 1.
+                 No map ships with the code.  More than 4 classes: the weighted CE only (KD_HARD_LOSS unset), an fp32 teacher
 Launch with `python -m torch.distributed.run --nproc-per-node N` for data-parallel training: one process per GPU,
 frames sharded over ranks in equal counts (every rank runs the same number of steps), rank 0's initial weights
 broadcast, gradients all-reduced in buckets during backward (CE and KD training alike), BatchNorm statistics per
@@ -90,14 +95,44 @@ def feature_loss_from_env(env=os.environ):
     return ChannelKD(tau=float(env.get("KD_CWD_TAU", 4.0)))
 
 
+def multiclass_from_env(env=os.environ):
+    """KD_NUM_CLASSES / KD_CLASS_MAP -> (num_classes, class_map): (None, None) with both unset -- nothing changes then"""
+    n, path = env.get("KD_NUM_CLASSES", ""), env.get("KD_CLASS_MAP", "")
+    if not n and not path:
+        return None, None
+    class_map = None
+    if path:
+        with open(path) as f:
+            raw = json.load(f)
+        if not isinstance(raw, dict) or not raw:
+            raise ValueError(f"KD_CLASS_MAP: {path} must hold a non-empty JSON object {{\"raw id\": class, ...}}")
+        try:
+            class_map = {int(k): v for k, v in raw.items()}
+        except ValueError:
+            raise ValueError(f"KD_CLASS_MAP: {path}: the keys must be raw class ids (integers)") from None
+        from src.data_loading.pandaset_dataset import class_map_table
+        top = int(class_map_table(class_map).max())          # validates the map (ValueError)
+    try:
+        num_classes = int(n) if n else max(2, top + 1)
+    except ValueError:
+        raise ValueError(f"KD_NUM_CLASSES must be an integer in [2, 16], got {n!r}") from None
+    if not 2 <= num_classes <= 16:
+        raise ValueError(f"KD_NUM_CLASSES must be an integer in [2, 16], got {num_classes}")
+    if class_map is not None and top >= num_classes:
+        raise ValueError(f"KD_CLASS_MAP names class {top}, KD_NUM_CLASSES={num_classes} allows 0..{num_classes - 1}")
+    return num_classes, class_map
+
+
 def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, val_scenes, device):
     log(f"\n{'='*80}\nTRAINING: {fusion_type.upper()} FUSION\n{'='*80}")
+    num_classes, class_map = multiclass_from_env()           # (None, None): the 2-class task, every call below as it was
+    mc = {} if class_map is None else {"class_map": class_map}
     train_loader, val_loader = create_pandaset_dataloaders(
         root=root, train_scenes=train_scenes, val_scenes=val_scenes,
-        batch_size=int(os.environ.get("KD_BATCH_SIZE", 4)), num_workers=2, verbose=False)
+        batch_size=int(os.environ.get("KD_BATCH_SIZE", 4)), num_workers=2, verbose=False, **mc)
     teacher_ckpt = os.environ.get("KD_TEACHER")
     base = int(os.environ.get("KD_STUDENT_BASE_CHANNELS", 32)) if teacher_ckpt else 32
-    model = build_model(fusion_type, fusion_out_channels, device, base_channels=base)
+    model = build_model(fusion_type, fusion_out_channels, device, num_classes=num_classes or 2, base_channels=base)
     summary = model.get_architecture_summary()
     log(f"\nModel: {fusion_type}\n  Total params: {summary['total_params']}\n  Fusion params: {summary['fusion_params']}")
     if base != 32:
@@ -106,11 +141,14 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
               class_weights=[0.4, 3.5], num_epochs=int(os.environ.get("KD_EPOCHS", 20)),
               max_grad_norm=float(os.environ["KD_MAX_GRAD_NORM"]) if os.environ.get("KD_MAX_GRAD_NORM") else None)
     kw["hard_loss"] = hard_loss_from_env()
+    if num_classes is not None:
+        kw.update(num_classes=num_classes, class_weights=[0.4] + [3.5] * (num_classes - 1))
+        log(f"  Classes: {num_classes} (KD_NUM_CLASSES / KD_CLASS_MAP)")
     kw.update(optim_options_from_env())        # KD_EMA_DECAY, KD_EMA_WARMUP, KD_NO_DECAY_NORM_BIAS, KD_LR_MULT, KD_ACCUM_STEPS: all unset = {}
     if kw["hard_loss"] is not None:
         log(f"  Hard-label loss: {kw['hard_loss']}")
     if teacher_ckpt:
-        teacher = build_model("concat", 256, device)
+        teacher = build_model("concat", 256, device, num_classes=num_classes or 2)
         teacher.load_state_dict(torch.load(teacher_ckpt, map_location=device)["model_state"])
         feature_loss = feature_loss_from_env()
         if feature_loss is not None:
