@@ -349,6 +349,26 @@ int kd_bilinear_sum_fwd(const float* in0, const float* sc0, const float* sh0, in
 int kd_bilinear_bwd(const float* dout, const float* in, const float* sc, const float* sh, int act,
                     const float* mean, const float* invstd, float* gin, float* partial, int B, int Hi, int Wi,
                     int Ho, int Wo, int C, void* stream);
+/* Inference: the FPN lateral at the output size writes the FPN sum itself.  out[B*Ho*Wo, N] = (act0((A . W^T + bias) * esc + esh)
+ * + 0.f) + resize(act1(in1 * sc1 + sh1)) (+ resize(act2(in2 * sc2 + sh2)); in2 == NULL: absent), in_t = [B, H_t, W_t, N]: the bits
+ * of kd_pwconv_gemm (pro 0, epi 0) followed by kd_bilinear_sum_fwd; the raw lateral map is never written.  A = [B*Ho*Wo, K] with
+ * row stride lda.  Covered (kd_pwconv_gemm_fpn_sum_supported, else KD_ERR_SHAPE and nothing is written): K = 64, N = 128, one
+ * or two smaller laterals of any size, split arithmetic with the streaming kernels on. */
+int kd_pwconv_gemm_fpn_sum_supported(int64_t M, int K, int N, int nlat);
+int kd_pwconv_gemm_fpn_sum(const float* A, int64_t lda, const float* W, const float* bias, const float* esc, const float* esh,
+                           int act0, const float* in1, const float* sc1, const float* sh1, int act1, int H1, int W1,
+                           const float* in2, const float* sc2, const float* sh2, int act2, int H2, int W2, float* out, int B,
+                           int Ho, int Wo, int K, int N, void* stream);
+/* 1 (default): a lateral of exactly half the output size takes the quad body of kd_bilinear_sum_fwd and the 4 x 4 window form
+ * of kd_bilinear_bwd / kd_bilinear_bwd2; 0: the general per-pixel bodies for every geometry.  The same bits either way.
+ * Returns the previous mode. */
+int kd_set_bilinear_2x_mode(int mode);
+/* kd_bilinear_bwd for two laterals of one geometry [B,Hi,Wi,C] under the same dout: dout is read once; gin_i and partial_i
+ * are bit-identical to two kd_bilinear_bwd launches */
+int kd_bilinear_bwd2(const float* dout, const float* in0, const float* sc0, const float* sh0, int act0, const float* mean0,
+                     const float* invstd0, float* gin0, float* partial0, const float* in1, const float* sc1, const float* sh1,
+                     int act1, const float* mean1, const float* invstd1, float* gin1, float* partial1, int B, int Hi, int Wi,
+                     int Ho, int Wo, int C, void* stream);
 int kd_weighted_fuse_fwd(const float* cat, const float* sc, const float* sh, const float* hraw, const float* w2,
                          const float* b2, float* out, float* wts, int64_t M, int C, void* stream);
 size_t kd_weighted_fuse_bwd_ws_bytes(int64_t M, int C);

@@ -98,6 +98,28 @@ __device__ __forceinline__ float4 kd_affine_act4(float4 x, float4 sc, float4 sh,
   return r;
 }
 
+// aten area_pixel_compute_source_index (align_corners=False, linear) + the index/lambda pair
+__device__ __forceinline__ void kd_bl_src(int o, int in_size, float scale, int& i0, int& i1, float& l0, float& l1) {
+  float src = scale * ((float)o + 0.5f) - 0.5f;
+  if (src < 0.f) src = 0.f;
+  i0 = (int)src;
+  if (i0 > in_size - 1) i0 = in_size - 1;
+  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+  l1 = src - (float)i0;
+  l0 = 1.f - l1;
+}
+// the bilinear blend of one term, in ONE spelling for every kernel that must give the bits of bilinear_sum_fwd_kernel (kd_fuse.hip, the
+// FPN-sum epilogue of pw_stream_kernel): one contraction into fused multiply-adds
+__device__ __forceinline__ float4 kd_bl_mix4(float lh0, float lh1, float lw0, float lw1, const float4& v00, const float4& v01,
+                                          const float4& v10, const float4& v11) {
+  float4 v;
+  v.x = lh0 * (lw0 * v00.x + lw1 * v01.x) + lh1 * (lw0 * v10.x + lw1 * v11.x);
+  v.y = lh0 * (lw0 * v00.y + lw1 * v01.y) + lh1 * (lw0 * v10.y + lw1 * v11.y);
+  v.z = lh0 * (lw0 * v00.z + lw1 * v01.z) + lh1 * (lw0 * v10.z + lw1 * v11.z);
+  v.w = lh0 * (lw0 * v00.w + lw1 * v01.w) + lh1 * (lw0 * v10.w + lw1 * v11.w);
+  return v;
+}
+
 // backward operand: dy_raw = al*(d*mask(z)) + be*x + ga with z = x*sc+sh  (al/be/ga from
 // kd_bn_bwd_finalize).  With act == NONE the mask is 1 and sc/sh are not read.
 __device__ __forceinline__ float kd_bwd_operand(float d, float x, float al, float be, float ga,

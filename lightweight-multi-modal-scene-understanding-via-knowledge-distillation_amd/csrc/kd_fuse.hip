@@ -8,17 +8,6 @@
 
 namespace {
 
-// aten area_pixel_compute_source_index (align_corners=False, linear) + the index/lambda pair
-__device__ __forceinline__ void bl_src(int o, int in_size, float scale, int& i0, int& i1, float& l0, float& l1) {
-  float src = scale * ((float)o + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
-
 struct BlArgs {
   const float* in; const float* sc; const float* sh; int act;     // deferred [B,Hi,Wi,C]
   float* out; int accumulate;                                      // [B,Ho,Wo,C]
@@ -38,8 +27,8 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(BlArgs a) {
     const int wo = (int)(p % a.Wo), ho = (int)((p / a.Wo) % a.Ho), b = (int)(p / ((int64_t)a.Wo * a.Ho));
     int h0, h1, w0, w1;
     float lh0, lh1, lw0, lw1;
-    bl_src(ho, a.Hi, a.sh_, h0, h1, lh0, lh1);
-    bl_src(wo, a.Wi, a.sw_, w0, w1, lw0, lw1);
+    kd_bl_src(ho, a.Hi, a.sh_, h0, h1, lh0, lh1);
+    kd_bl_src(wo, a.Wi, a.sw_, w0, w1, lw0, lw1);
     const float* base = a.in + (int64_t)b * a.Hi * a.Wi * a.C + c0;
     const float4 v00 = kd_affine_act4(kd_ld4(base + ((int64_t)h0 * a.Wi + w0) * a.C), sc, sh, a.act);
     const float4 v01 = kd_affine_act4(kd_ld4(base + ((int64_t)h0 * a.Wi + w1) * a.C), sc, sh, a.act);
@@ -66,6 +55,83 @@ struct Bl3Args {
   const float* in[3]; const float* sc[3]; const float* sh[3]; int act[3]; int Hi[3], Wi[3]; float shh[3], sww[3]; int nin;
   float* out; int B, Ho, Wo, C, groups, slots;
 };
+__device__ __forceinline__ float4 bl_sel4(bool s, const float4& x, const float4& y) {
+  return make_float4(s ? x.x : y.x, s ? x.y : y.y, s ? x.z : y.z, s ? x.w : y.w);
+}
+
+// Source indices and weights of the output pair (o, o + 1), o even, along one axis of a lateral of exactly half the output size.
+// scale is 0.5, so src is o/2 - 0.25 and o/2 + 0.25 without rounding: the pair touches at most three source indices,
+// i[0] = i0(o), i[1] = i1(o), i[2] = i1(o + 1), and i0(o + 1) is i[1] -- or i[0] for the first pair, where src clamps to 0.
+struct BlPair { int i[3]; bool first; float la0, la1, lb0, lb1; };
+__device__ __forceinline__ BlPair bl_pair(int o, int in_size) {
+  BlPair x;
+  int b0;
+  kd_bl_src(o, in_size, 0.5f, x.i[0], x.i[1], x.la0, x.la1);
+  kd_bl_src(o + 1, in_size, 0.5f, b0, x.i[2], x.lb0, x.lb1);
+  x.first = b0 == x.i[0];
+  return x;
+}
+
+// The FPN sum with one 2x2 quad of output pixels per thread, for lateral 0 at the output size with an activation (the one-load
+// form of the per-pixel body below) and laterals 1..NIN-1 at exactly half of it: a half-size lateral's 3x3 source window is loaded
+// (and activated) once for the quad instead of 2x2 texels per pixel, and all loads of a quad are issued before its arithmetic.
+// Each output takes the same texels, weights, expression and term order as in the per-pixel body: the same bits.
+template <int NIN>
+__global__ __launch_bounds__(256) void bilinear_sum_fwd_quad_kernel(Bl3Args a) {
+  const int tid = threadIdx.x;
+  const int gidx = tid % a.groups, slot = tid / a.groups;
+  if (slot >= a.slots) return;
+  const int c0 = gidx * 4;
+  float4 sc[NIN], sh[NIN];
+#pragma unroll
+  for (int t = 0; t < NIN; ++t) {
+    sc[t] = make_float4(1.f, 1.f, 1.f, 1.f); sh[t] = kd_zero4();
+    if (a.sc[t]) { sc[t] = kd_ld4(a.sc[t] + c0); sh[t] = kd_ld4(a.sh[t] + c0); }
+  }
+  const int Hq = a.Ho / 2, Wq = a.Wo / 2;
+  const int64_t nquad = (int64_t)a.B * Hq * Wq;
+  for (int64_t q = (int64_t)blockIdx.x * a.slots + slot; q < nquad; q += (int64_t)gridDim.x * a.slots) {
+    const int wo = 2 * (int)(q % Wq), ho = 2 * (int)((q / Wq) % Hq), b = (int)(q / ((int64_t)Wq * Hq));
+    const int64_t o00 = (((int64_t)b * a.Ho + ho) * a.Wo + wo) * a.C + c0;        // the quad's first pixel in a full-size map
+    const BlPair H = bl_pair(ho, Hq), W = bl_pair(wo, Wq);
+    float4 x0[4], x[NIN - 1][9];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x0[k] = kd_ld4(a.in[0] + o00 + ((int64_t)(k >> 1) * a.Wo + (k & 1)) * a.C);
+#pragma unroll
+    for (int t = 1; t < NIN; ++t) {
+      const float* base = a.in[t] + (int64_t)b * Hq * Wq * a.C + c0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) x[t - 1][k] = kd_ld4(base + ((int64_t)H.i[k / 3] * Wq + W.i[k % 3]) * a.C);
+    }
+    float4 r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float4 y = kd_affine_act4(x0[k], sc[0], sh[0], a.act[0]);
+      r[k] = make_float4(y.x + 0.f, y.y + 0.f, y.z + 0.f, y.w + 0.f);
+    }
+#pragma unroll
+    for (int t = 1; t < NIN; ++t) {
+      float4 y[3][3], cb[3], rb[3], v[4];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) y[k / 3][k % 3] = kd_affine_act4(x[t - 1][k], sc[t], sh[t], a.act[t]);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        cb[k] = bl_sel4(W.first, y[k][0], y[k][1]);            // column i0(wo + 1) of source row k
+        rb[k] = bl_sel4(H.first, y[0][k], y[1][k]);            // row i0(ho + 1) at source column k
+      }
+      const float4 rcb = bl_sel4(H.first, cb[0], cb[1]);
+      v[0] = kd_bl_mix4(H.la0, H.la1, W.la0, W.la1, y[0][0], y[0][1], y[1][0], y[1][1]);
+      v[1] = kd_bl_mix4(H.la0, H.la1, W.lb0, W.lb1, cb[0], y[0][2], cb[1], y[1][2]);
+      v[2] = kd_bl_mix4(H.lb0, H.lb1, W.la0, W.la1, rb[0], rb[1], y[2][0], y[2][1]);
+      v[3] = kd_bl_mix4(H.lb0, H.lb1, W.lb0, W.lb1, rcb, rb[2], cb[2], y[2][2]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { r[k].x = v[k].x + r[k].x; r[k].y = v[k].y + r[k].y; r[k].z = v[k].z + r[k].z; r[k].w = v[k].w + r[k].w; }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) kd_st4(a.out + o00 + ((int64_t)(k >> 1) * a.Wo + (k & 1)) * a.C, r[k]);
+  }
+}
+
 __global__ __launch_bounds__(256) void bilinear_sum_fwd_kernel(Bl3Args a) {
   const int tid = threadIdx.x;
   const int gidx = tid % a.groups, slot = tid / a.groups;
@@ -86,8 +152,8 @@ __global__ __launch_bounds__(256) void bilinear_sum_fwd_kernel(Bl3Args a) {
       if (t < a.nin) {
         int h0, h1, w0, w1;
         float lh0, lh1, lw0, lw1;
-        bl_src(ho, a.Hi[t], a.shh[t], h0, h1, lh0, lh1);
-        bl_src(wo, a.Wi[t], a.sww[t], w0, w1, lw0, lw1);
+        kd_bl_src(ho, a.Hi[t], a.shh[t], h0, h1, lh0, lh1);
+        kd_bl_src(wo, a.Wi[t], a.sww[t], w0, w1, lw0, lw1);
         const float* base = a.in[t] + (int64_t)b * a.Hi[t] * a.Wi[t] * a.C + c0;
         const float4 v00 = kd_affine_act4(kd_ld4(base + ((int64_t)h0 * a.Wi[t] + w0) * a.C), sc[t], sh[t], a.act[t]);
         float4 v;
@@ -100,10 +166,7 @@ __global__ __launch_bounds__(256) void bilinear_sum_fwd_kernel(Bl3Args a) {
           const float4 v01 = kd_affine_act4(kd_ld4(base + ((int64_t)h0 * a.Wi[t] + w1) * a.C), sc[t], sh[t], a.act[t]);
           const float4 v10 = kd_affine_act4(kd_ld4(base + ((int64_t)h1 * a.Wi[t] + w0) * a.C), sc[t], sh[t], a.act[t]);
           const float4 v11 = kd_affine_act4(kd_ld4(base + ((int64_t)h1 * a.Wi[t] + w1) * a.C), sc[t], sh[t], a.act[t]);
-          v.x = lh0 * (lw0 * v00.x + lw1 * v01.x) + lh1 * (lw0 * v10.x + lw1 * v11.x);
-          v.y = lh0 * (lw0 * v00.y + lw1 * v01.y) + lh1 * (lw0 * v10.y + lw1 * v11.y);
-          v.z = lh0 * (lw0 * v00.z + lw1 * v01.z) + lh1 * (lw0 * v10.z + lw1 * v11.z);
-          v.w = lh0 * (lw0 * v00.w + lw1 * v01.w) + lh1 * (lw0 * v10.w + lw1 * v11.w);
+          v = kd_bl_mix4(lh0, lh1, lw0, lw1, v00, v01, v10, v11);
         }
         if (t == 0) r = v; else { r.x = v.x + r.x; r.y = v.y + r.y; r.z = v.z + r.z; r.w = v.w + r.w; }
       }
@@ -115,22 +178,39 @@ __global__ __launch_bounds__(256) void bilinear_sum_fwd_kernel(Bl3Args a) {
 __device__ __forceinline__ float bl_weight(int o, int i, int in_size, float scale) {
   int i0, i1;
   float l0, l1;
-  bl_src(o, in_size, scale, i0, i1, l0, l1);
+  kd_bl_src(o, in_size, scale, i0, i1, l0, l1);
   return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
 }
 
 // adjoint (gather form, deterministic): gin[b,hi,wi,c] = mask * sum_{ho,wo} W(ho,hi) W(wo,wi) dout[b,ho,wo,c]
-__global__ __launch_bounds__(256) void bilinear_bwd_kernel(BlArgs a) {
+// NL laterals of one geometry in one launch (NL = 2: kd_bilinear_bwd2): each dout window is loaded once and applied to every
+// lateral's mask.  Grid, groups / slots mapping, per-thread pixel sets and summation order do not depend on NL, so gin and
+// partial of each lateral are the bits of a launch of its own.
+template <int NL>
+struct BlBwdArgs {
+  const float* dout; const float* in[NL]; const float* sc[NL]; const float* sh[NL]; int act[NL];
+  const float* mean[NL]; const float* invstd[NL]; float* gin[NL]; float* partial[NL];
+  int B, Hi, Wi, Ho, Wo, C; float sh_, sw_; int groups, slots;
+};
+// WIN: Ho = 2 Hi and Wo = 2 Wi, the 4 x 4 window form (an instance of its own: the general loop keeps its 62 registers)
+template <int NL, bool WIN>
+__global__ __launch_bounds__(256) void bilinear_bwd_kernel(BlBwdArgs<NL> a) {
   __shared__ float red[2 * 256 * 4];
   const int tid = threadIdx.x;
   const int gidx = tid % a.groups, slot = tid / a.groups;
   const bool active = slot < a.slots;
   const int c0 = gidx * 4;
-  float4 s1 = kd_zero4(), s2 = kd_zero4();
+  float4 s1[NL], s2[NL];
+#pragma unroll
+  for (int l = 0; l < NL; ++l) { s1[l] = kd_zero4(); s2[l] = kd_zero4(); }
   if (active) {
-    float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = kd_zero4(), mu = kd_zero4(), inv = kd_zero4();
-    if (a.sc) { sc = kd_ld4(a.sc + c0); sh = kd_ld4(a.sh + c0); }
-    if (a.mean) { mu = kd_ld4(a.mean + c0); inv = kd_ld4(a.invstd + c0); }
+    float4 sc[NL], sh[NL], mu[NL], inv[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+      sc[l] = make_float4(1.f, 1.f, 1.f, 1.f); sh[l] = kd_zero4(); mu[l] = kd_zero4(); inv[l] = kd_zero4();
+      if (a.sc[l]) { sc[l] = kd_ld4(a.sc[l] + c0); sh[l] = kd_ld4(a.sh[l] + c0); }
+      if (a.mean[l]) { mu[l] = kd_ld4(a.mean[l] + c0); inv[l] = kd_ld4(a.invstd[l] + c0); }
+    }
     const int64_t npix = (int64_t)a.B * a.Hi * a.Wi;
     for (int64_t p = (int64_t)blockIdx.x * a.slots + slot; p < npix; p += (int64_t)gridDim.x * a.slots) {
       const int wi = (int)(p % a.Wi), hi = (int)((p / a.Wi) % a.Hi), b = (int)(p / ((int64_t)a.Wi * a.Hi));
@@ -144,6 +224,31 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(BlArgs a) {
       if (a.Hi == a.Ho && a.Wi == a.Wo) {              // same size: the adjoint is the identity (fma(1, d, 0) = d: the bits of the general loop)
         acc = kd_ld4(a.dout + p * a.C + c0);
         olo = 1; ohi = 0;                               // (skips the gather loops below)
+      } else if constexpr (WIN) {
+        // exactly half the output size: src(o) = o / 2 - 0.25 without rounding, so the nonzero weights of input index i are those
+        // of o = 2i - 1 .. 2i + 2 (inside the map) and nothing else in [olo, ohi].  The 4 x 4 window is loaded up front -- sixteen
+        // loads in flight instead of one per turn of a loop with two data-dependent skips -- and applied in the loop's order with
+        // the loop's weights and skips: the same bits.
+        float wh[4], ww[4];
+        int oh[4], ow[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int o = 2 * hi - 1 + i, q = 2 * wi - 1 + i;
+          const bool okh = o >= 0 && o < a.Ho, okw = q >= 0 && q < a.Wo;
+          oh[i] = okh ? o : 2 * hi; ow[i] = okw ? q : 2 * wi;
+          wh[i] = okh ? bl_weight(o, hi, a.Hi, a.sh_) : 0.f;
+          ww[i] = okw ? bl_weight(q, wi, a.Wi, a.sw_) : 0.f;
+        }
+        float4 d[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) d[k] = kd_ld4(a.dout + (((int64_t)b * a.Ho + oh[k >> 2]) * a.Wo + ow[k & 3]) * a.C + c0);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          if (wh[k >> 2] == 0.f || ww[k & 3] == 0.f) continue;
+          const float w = wh[k >> 2] * ww[k & 3];
+          acc.x = fmaf(w, d[k].x, acc.x); acc.y = fmaf(w, d[k].y, acc.y); acc.z = fmaf(w, d[k].z, acc.z); acc.w = fmaf(w, d[k].w, acc.w);
+        }
+        olo = 1; ohi = 0;
       }
       for (int oh = olo; oh <= ohi; ++oh) {
         const float wh = bl_weight(oh, hi, a.Hi, a.sh_);
@@ -156,30 +261,37 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(BlArgs a) {
           acc.x = fmaf(w, d.x, acc.x); acc.y = fmaf(w, d.y, acc.y); acc.z = fmaf(w, d.z, acc.z); acc.w = fmaf(w, d.w, acc.w);
         }
       }
-      if (a.sc) {
-        const float4 xr = kd_ld4(a.in + p * a.C + c0);
-        acc.x *= kd_act_mask(kd_affine(xr.x, sc.x, sh.x), a.act);
-        acc.y *= kd_act_mask(kd_affine(xr.y, sc.y, sh.y), a.act);
-        acc.z *= kd_act_mask(kd_affine(xr.z, sc.z, sh.z), a.act);
-        acc.w *= kd_act_mask(kd_affine(xr.w, sc.w, sh.w), a.act);
-        s1.x += acc.x; s1.y += acc.y; s1.z += acc.z; s1.w += acc.w;
-        s2.x = fmaf(acc.x, (xr.x - mu.x) * inv.x, s2.x);
-        s2.y = fmaf(acc.y, (xr.y - mu.y) * inv.y, s2.y);
-        s2.z = fmaf(acc.z, (xr.z - mu.z) * inv.z, s2.z);
-        s2.w = fmaf(acc.w, (xr.w - mu.w) * inv.w, s2.w);
+#pragma unroll
+      for (int l = 0; l < NL; ++l) {
+        float4 g = acc;                                 // the gathered adjoint is the same for every lateral; the mask is not
+        if (a.sc[l]) {
+          const float4 xr = kd_ld4(a.in[l] + p * a.C + c0);
+          g.x *= kd_act_mask(kd_affine(xr.x, sc[l].x, sh[l].x), a.act[l]);
+          g.y *= kd_act_mask(kd_affine(xr.y, sc[l].y, sh[l].y), a.act[l]);
+          g.z *= kd_act_mask(kd_affine(xr.z, sc[l].z, sh[l].z), a.act[l]);
+          g.w *= kd_act_mask(kd_affine(xr.w, sc[l].w, sh[l].w), a.act[l]);
+          s1[l].x += g.x; s1[l].y += g.y; s1[l].z += g.z; s1[l].w += g.w;
+          s2[l].x = fmaf(g.x, (xr.x - mu[l].x) * inv[l].x, s2[l].x);
+          s2[l].y = fmaf(g.y, (xr.y - mu[l].y) * inv[l].y, s2[l].y);
+          s2[l].z = fmaf(g.z, (xr.z - mu[l].z) * inv[l].z, s2[l].z);
+          s2[l].w = fmaf(g.w, (xr.w - mu[l].w) * inv[l].w, s2[l].w);
+        }
+        kd_st4(a.gin[l] + p * a.C + c0, g);
       }
-      kd_st4(a.gin + p * a.C + c0, acc);
     }
   }
-  if (a.partial) {
-    kd_st4(red + tid * 4, s1);
-    kd_st4(red + 1024 + tid * 4, s2);
+#pragma unroll
+  for (int l = 0; l < NL; ++l) {
+    if (!a.partial[l]) continue;                        // (block-uniform)
+    if (l) __syncthreads();                             // the previous lateral's readers are done with red
+    kd_st4(red + tid * 4, s1[l]);
+    kd_st4(red + 1024 + tid * 4, s2[l]);
     __syncthreads();
     for (int i = tid; i < 2 * a.C; i += 256) {
       const int st = i / a.C, c = i % a.C;
       float s = 0.f;
       for (int sl = 0; sl < a.slots; ++sl) s += red[st * 1024 + (sl * a.groups + c / 4) * 4 + (c & 3)];
-      a.partial[((int64_t)blockIdx.x * 2 + st) * a.C + c] = s;
+      a.partial[l][((int64_t)blockIdx.x * 2 + st) * a.C + c] = s;
     }
   }
 }
@@ -413,7 +525,13 @@ __global__ __launch_bounds__(256) void cls_bwd_kernel(ClsArgs a) {
 
 }  // namespace
 
+// kd_set_bilinear_2x_mode: 1 (default) the exact-2x forms -- the quad body of the FPN sum, the window form of the adjoint;
+// 0 the general per-pixel bodies for every geometry (the same bits: tests/test_gpu_fpn_lateral_sum.py compares the two)
+static std::atomic<int> g_bl_2x{1};
+
 extern "C" {
+
+int kd_set_bilinear_2x_mode(int mode) { return g_bl_2x.exchange(mode != 0); }
 
 // out (+)= bilinear_resize(act(in*sc+sh)) ; align_corners=False; identity when sizes match.
 int kd_bilinear_accum_fwd(const float* in, const float* sc, const float* sh, int act, float* out, int accumulate,
@@ -446,6 +564,16 @@ int kd_bilinear_sum_fwd(const float* in0, const float* sc0, const float* sh0, in
       ++a.nin;
     }
   a.out = out; a.B = B; a.Ho = Ho; a.Wo = Wo; a.C = C; a.groups = l.groups; a.slots = l.slots;
+  // the quad body: lateral 0 at the (even) output size with an activation, one or two more laterals at exactly half of it
+  bool quad = g_bl_2x.load(std::memory_order_relaxed) && a.nin >= 2 && Ho % 2 == 0 && Wo % 2 == 0 && a.Hi[0] == Ho && a.Wi[0] == Wo && a.act[0] != KD_ACT_NONE;
+  for (int t = 1; t < a.nin; ++t) quad = quad && 2 * a.Hi[t] == Ho && 2 * a.Wi[t] == Wo;
+  if (quad) {
+    const KdCgLayout lq = kd_cg_layout((int64_t)B * (Ho / 2) * (Wo / 2), C);
+    a.groups = lq.groups; a.slots = lq.slots;
+    if (a.nin == 2) hipLaunchKernelGGL(bilinear_sum_fwd_quad_kernel<2>, dim3(lq.grid), dim3(256), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(bilinear_sum_fwd_quad_kernel<3>, dim3(lq.grid), dim3(256), 0, (hipStream_t)stream, a);
+    return kd_check_launch("kd_bilinear_sum_fwd");
+  }
   hipLaunchKernelGGL(bilinear_sum_fwd_kernel, dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
   return kd_check_launch("kd_bilinear_sum_fwd");
 }
@@ -457,10 +585,32 @@ int kd_bilinear_bwd(const float* dout, const float* in, const float* sc, const f
   KD_REQUIRE(dout && gin && B > 0 && C % 4 == 0 && C <= 1024, KD_ERR_ARG, "kd_bilinear_bwd: bad args");
   KD_REQUIRE(!sc || (in && sh && (!partial || (mean && invstd))), KD_ERR_ARG, "kd_bilinear_bwd: mask needs in/sh (+mean/invstd)");
   const KdCgLayout l = kd_cg_layout((int64_t)B * Hi * Wi, C);
-  BlArgs a{in, sc, sh, act, nullptr, 0, dout, mean, invstd, gin, sc ? partial : nullptr, B, Hi, Wi, Ho, Wo, C,
-           (float)Hi / (float)Ho, (float)Wi / (float)Wo, l.groups, l.slots};
-  hipLaunchKernelGGL(bilinear_bwd_kernel, dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  BlBwdArgs<1> a{dout, {in}, {sc}, {sh}, {act}, {mean}, {invstd}, {gin}, {sc ? partial : nullptr}, B, Hi, Wi, Ho, Wo, C,
+                 (float)Hi / (float)Ho, (float)Wi / (float)Wo, l.groups, l.slots};
+  if (g_bl_2x.load(std::memory_order_relaxed) && Ho == 2 * Hi && Wo == 2 * Wi)
+    hipLaunchKernelGGL((bilinear_bwd_kernel<1, true>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((bilinear_bwd_kernel<1, false>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
   return kd_check_launch("kd_bilinear_bwd");
+}
+
+// kd_bilinear_bwd for two laterals of one geometry that take the same dout: one read of dout, the bits of two launches.
+int kd_bilinear_bwd2(const float* dout, const float* in0, const float* sc0, const float* sh0, int act0, const float* mean0,
+                     const float* invstd0, float* gin0, float* partial0, const float* in1, const float* sc1, const float* sh1,
+                     int act1, const float* mean1, const float* invstd1, float* gin1, float* partial1, int B, int Hi, int Wi,
+                     int Ho, int Wo, int C, void* stream) {
+  KD_REQUIRE(dout && gin0 && gin1 && gin0 != gin1 && B > 0 && C % 4 == 0 && C <= 1024, KD_ERR_ARG, "kd_bilinear_bwd2: bad args");
+  KD_REQUIRE(!sc0 || (in0 && sh0 && (!partial0 || (mean0 && invstd0))), KD_ERR_ARG, "kd_bilinear_bwd2: mask 0 needs in/sh (+mean/invstd)");
+  KD_REQUIRE(!sc1 || (in1 && sh1 && (!partial1 || (mean1 && invstd1))), KD_ERR_ARG, "kd_bilinear_bwd2: mask 1 needs in/sh (+mean/invstd)");
+  const KdCgLayout l = kd_cg_layout((int64_t)B * Hi * Wi, C);
+  BlBwdArgs<2> a{dout, {in0, in1}, {sc0, sc1}, {sh0, sh1}, {act0, act1}, {mean0, mean1}, {invstd0, invstd1}, {gin0, gin1},
+                 {sc0 ? partial0 : nullptr, sc1 ? partial1 : nullptr}, B, Hi, Wi, Ho, Wo, C,
+                 (float)Hi / (float)Ho, (float)Wi / (float)Wo, l.groups, l.slots};
+  if (g_bl_2x.load(std::memory_order_relaxed) && Ho == 2 * Hi && Wo == 2 * Wi)
+    hipLaunchKernelGGL((bilinear_bwd_kernel<2, true>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL((bilinear_bwd_kernel<2, false>), dim3(l.grid), dim3(256), 0, (hipStream_t)stream, a);
+  return kd_check_launch("kd_bilinear_bwd2");
 }
 
 static int wf_lp(int C) { return (C == 32 || C == 64 || C == 128 || C == 256) ? C / 4 : 0; }

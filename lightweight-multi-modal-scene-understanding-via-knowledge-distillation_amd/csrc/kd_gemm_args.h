@@ -27,6 +27,11 @@ struct GemmArgs {
   // weight gradient that depends on this GEMM's result); with it set, C may be NULL and G0 is never stored.
   float* m1slab;
   int nt_store;                       // C is large (>= 64 MB): store it with the non-temporal hint
+  // EPI6 only (kd_pwconv_gemm_fpn_sum): this GEMM is the FPN lateral at the output size; matrix row m is pixel (b, ho, wo) of a
+  // [B, fHo, fWo] map and the epilogue adds the bilinear terms of fn smaller deferred laterals fin[t] = [B, fH[t], fW[t], N]
+  // (coefficients fsc / fsh [N], activation fact, fsy = fH / fHo and fsx = fW / fWo as floats), as bilinear_sum_fwd_kernel does.
+  const float* fin[2]; const float* fsc[2]; const float* fsh[2]; int fact[2]; int fH[2], fW[2]; float fsy[2], fsx[2];
+  int fn, fHo, fWo;
 };
 
 

@@ -118,4 +118,53 @@ int kd_gemm_stream_launch(GemmArgs& g, int pro, int epi, hipStream_t st) {
   return rc;
 }
 
+// ---- the FPN sum written by the output-size lateral's GEMM (inference) ------------------------------------------------------
+// out[m] = (act0(affine(A[m] . W^T + bias, esc, esh)) + 0.f) + resize(lateral 1)[m] (+ resize(lateral 2)[m]), the bits of
+// kd_pwconv_gemm (raw) followed by kd_bilinear_sum_fwd, without the [M, N] raw map in between.  One instance: the model's
+// 64 -> 128 lateral on a dense input (pro 0) in the split arithmetic, the streaming kernel with one 128-wide column tile and the
+// transposed store; everything else is refused (the caller keeps the two launches).
+int kd_gemm_split_mode();
+
+extern "C" {
+
+int kd_pwconv_gemm_fpn_sum_supported(int64_t M, int K, int N, int nlat) {
+  StreamCfg c;
+  return kd_gemm_split_mode() && M > 0 && M < ((int64_t)1 << 31) && K == 64 && N == 128 && (nlat == 1 || nlat == 2) &&
+         stream_cfg(K, N, 0, 0, false, c) && c.kb == 2 && c.nb == 4 && c.ntiles == 1;
+}
+
+int kd_pwconv_gemm_fpn_sum(const float* A, int64_t lda, const float* W, const float* bias, const float* esc, const float* esh,
+                           int act0, const float* in1, const float* sc1, const float* sh1, int act1, int H1, int W1,
+                           const float* in2, const float* sc2, const float* sh2, int act2, int H2, int W2, float* out, int B,
+                           int Ho, int Wo, int K, int N, void* stream) {
+  KD_REQUIRE(A && W && esc && esh && in1 && sc1 && sh1 && out && B > 0 && Ho > 0 && Wo > 0 && H1 > 0 && W1 > 0, KD_ERR_ARG,
+             "kd_pwconv_gemm_fpn_sum: null pointer or empty shape");
+  KD_REQUIRE(!in2 || (sc2 && sh2 && H2 > 0 && W2 > 0), KD_ERR_ARG, "kd_pwconv_gemm_fpn_sum: lateral 2 needs sc, sh and a size");
+  const int64_t M = (int64_t)B * Ho * Wo;
+  KD_REQUIRE(kd_pwconv_gemm_fpn_sum_supported(M, K, N, in2 ? 2 : 1), KD_ERR_SHAPE,
+             "kd_pwconv_gemm_fpn_sum: M=%lld K=%d N=%d is not covered (K = 64, N = 128, split arithmetic, streaming kernels on)",
+             (long long)M, K, N);
+  KD_REQUIRE(lda % 4 == 0 && lda >= K, KD_ERR_SHAPE, "kd_pwconv_gemm_fpn_sum: lda=%lld", (long long)lda);
+  KD_REQUIRE(kd_aligned16(A) && kd_aligned16(W) && kd_aligned16(out) && kd_aligned16(bias) && kd_aligned16(esc) && kd_aligned16(esh) &&
+             kd_aligned16(in1) && kd_aligned16(sc1) && kd_aligned16(sh1) && kd_aligned16(in2) && kd_aligned16(sc2) && kd_aligned16(sh2),
+             KD_ERR_ALIGN, "kd_pwconv_gemm_fpn_sum: every tensor must be 16-byte aligned");
+  GemmArgs g{};
+  g.A = A; g.lda = lda; g.W = W; g.bias = bias; g.C = out; g.ldc = N; g.esc = esc; g.esh = esh; g.epi_act = act0;
+  g.M = (int)M; g.K = K; g.N = N; g.nt_store = kd_nt_store((size_t)M * N * sizeof(float));
+  g.fin[0] = in1; g.fsc[0] = sc1; g.fsh[0] = sh1; g.fact[0] = act1; g.fH[0] = H1; g.fW[0] = W1;
+  g.fsy[0] = (float)H1 / (float)Ho; g.fsx[0] = (float)W1 / (float)Wo;
+  g.fn = 1; g.fHo = Ho; g.fWo = Wo;
+  if (in2) {
+    g.fin[1] = in2; g.fsc[1] = sc2; g.fsh[1] = sh2; g.fact[1] = act2; g.fH[1] = H2; g.fW[1] = W2;
+    g.fsy[1] = (float)H2 / (float)Ho; g.fsx[1] = (float)W2 / (float)Wo;
+    g.fn = 2;
+  }
+  const dim3 grid(stream_grid(M, 1), 1);
+  const int rc = stream_launch_one<2, 1, 4, 0, 6, true, false>(g, grid, (hipStream_t)stream);
+  if (rc < 0) return KD_ERR_ARG;
+  return kd_check_launch("kd_pwconv_gemm_fpn_sum");
+}
+
+}  // extern "C"
+
 extern "C" int kd_set_gemm_stream(int mode) { return g_stream_on.exchange(mode < 0 ? 0 : (mode > 3 ? 2 : mode)); }   // 0 off, 1 selective, 2 all, 3 forward only; returns the previous mode

@@ -78,6 +78,8 @@ constexpr size_t stream_lds_bytes(int K, int N, int pro) {
 // KB = K / 32, KC = chunk width / 32 (divides KB), NB = column-tile width / 32.
 // DB: two register sets per streamed tensor -- the loads of chunk c + 1 are issued BEFORE the k-loop of chunk c.
 // ADD: g.addend is added (EPI5: after BatchNorm + activation; otherwise to the raw result, before bias and mask).
+// EPI6 (kd_pwconv_gemm_fpn_sum, one instance): eval BatchNorm + activation, then the bilinear terms of the smaller FPN laterals are
+// added in the transposed store and the FPN sum is written instead of the lateral map (GemmArgs: f*).
 template <int KB, int KC, int NB, int PRO, int EPI, bool DB = false, bool ADD = false>
 __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
   constexpr int K = 32 * KB, N = 32 * NB, CPR = K / 8;
@@ -126,13 +128,13 @@ __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
   const int64_t wtot = (int64_t)gridDim.x * SW, wid = (int64_t)blockIdx.x * SW + wave;
 
   // per-lane column constants: column of block j is n0 + 32 j + r (N_total is a multiple of the tile width: no column tail)
-  constexpr int NE = (EPI == 5 || EPI_BWD) ? NB : 1;
+  constexpr int NE = (EPI == 5 || EPI == 6 || EPI_BWD) ? NB : 1;
   float bias[NB], esc[NE], esh[NE], emean[EPI_BWD ? NB : 1], einv[EPI_BWD ? NB : 1];
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
     const int c = n0 + 32 * j + r;
     bias[j] = g.bias ? g.bias[c] : 0.f;
-    if (EPI == 5 || EPI_BWD) { esc[j] = g.esc[c]; esh[j] = g.esh[c]; }
+    if (EPI == 5 || EPI == 6 || EPI_BWD) { esc[j] = g.esc[c]; esh[j] = g.esh[c]; }
     if (EPI_BWD) { emean[j] = g.emean[c]; einv[j] = g.einv[c]; }
   }
   constexpr int NS = (EPI == 1 || EPI_BWD) ? NB : 1;
@@ -281,6 +283,18 @@ __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
     constexpr int QG = NB >= 4 ? 8 : 16;         // (the split that keeps hipcc inside the register budget without spills)
     const int64_t m0 = s * 32;
     const float* addend = ADD ? g.addend : nullptr;
+    // EPI6: the pixels (b, ho, wo) of the four rows this lane stores per column block (rows past M: the last row's, for the loads only)
+    int fb[EPI == 6 ? 4 : 1], fho[EPI == 6 ? 4 : 1], fwo[EPI == 6 ? 4 : 1];
+    if constexpr (EPI == 6) {
+      static_assert(stream_tstore(KB, NB, PRO, EPI) && !ADD, "the FPN-sum epilogue lives in the transposed store");
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        int64_t gm = m0 + (lane >> 3) + 8 * p;
+        gm = (FULL || gm < M) ? gm : M - 1;
+        const unsigned um = (unsigned)gm, wo_ = (unsigned)g.fWo, ho_ = (unsigned)g.fHo;
+        fwo[p] = (int)(um % wo_); fho[p] = (int)((um / wo_) % ho_); fb[p] = (int)(um / (wo_ * ho_));
+      }
+    }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       float* cbase = g.C + m0 * g.ldc + n0 + 32 * j;               // wave-uniform
@@ -317,6 +331,7 @@ __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
             v = kd_act(kd_affine(v, esc[j], esh[j]), g.epi_act);
             if constexpr (ADD) v += ad[qi];
           }
+          if (EPI == 6) v = kd_act(kd_affine(v, esc[j], esh[j]), g.epi_act) + 0.f;   // the sum's first term (bilinear_sum_fwd_kernel: why + 0.f)
           if constexpr (EPI == 2) {
             const float x = xr[qi];
             v *= kd_act_mask(kd_affine(x, esc[j], esh[j]), g.epi_act);
@@ -340,8 +355,28 @@ __global__ __launch_bounds__(64 * SW, 2) void pw_stream_kernel(GemmArgs g) {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
           const int rr = tr0 + 8 * p;
-          const float4 v = kd_ld4(trt + rr * 36 + tc4);
+          float4 v = kd_ld4(trt + rr * 36 + tc4);
           float* dst = cbase + (int64_t)rr * g.ldc + tc4;
+          if constexpr (EPI == 6) {
+            // r = v_t + r for the smaller laterals, in order: the texels, weights and blend of bilinear_sum_fwd_kernel's per-pixel body
+            const int cn = n0 + 32 * j + tc4;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              if (t < g.fn) {                                            // (wave-uniform)
+                int h0, h1, w0, w1;
+                float lh0, lh1, lw0, lw1;
+                kd_bl_src(fho[p], g.fH[t], g.fsy[t], h0, h1, lh0, lh1);
+                kd_bl_src(fwo[p], g.fW[t], g.fsx[t], w0, w1, lw0, lw1);
+                const float* base = g.fin[t] + (int64_t)fb[p] * g.fH[t] * g.fW[t] * g.N + cn;
+                const float4 x00 = kd_ld4(base + ((int64_t)h0 * g.fW[t] + w0) * g.N), x01 = kd_ld4(base + ((int64_t)h0 * g.fW[t] + w1) * g.N);
+                const float4 x10 = kd_ld4(base + ((int64_t)h1 * g.fW[t] + w0) * g.N), x11 = kd_ld4(base + ((int64_t)h1 * g.fW[t] + w1) * g.N);
+                const float4 sc = kd_ld4(g.fsc[t] + cn), sh = kd_ld4(g.fsh[t] + cn);
+                const float4 u = kd_bl_mix4(lh0, lh1, lw0, lw1, kd_affine_act4(x00, sc, sh, g.fact[t]), kd_affine_act4(x01, sc, sh, g.fact[t]),
+                                            kd_affine_act4(x10, sc, sh, g.fact[t]), kd_affine_act4(x11, sc, sh, g.fact[t]));
+                v.x = u.x + v.x; v.y = u.y + v.y; v.z = u.z + v.z; v.w = u.w + v.w;
+              }
+            }
+          }
           if (FULL || m0 + rr < M) { if (g.nt_store) kd_st4_nt(dst, v); else kd_st4(dst, v); }
         }
       }

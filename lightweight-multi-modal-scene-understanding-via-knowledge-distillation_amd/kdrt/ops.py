@@ -208,6 +208,21 @@ def pw_gemm(A, W, C_out, *, M, K, N, A2=None, pro=0, pro_act=0, p=(None,) * 5, b
               4.0 * (M * K * (2 if pro == 2 else 1) + M * N * (1 + (epi == 2) + (addend is not None)) + N * K), m_dev, M)
 
 
+def pw_gemm_fpn_sum(A, W, bias, bnc0: BNC, act0, lats, out, geom):
+    """Inference FPN: out = act0(bn0(A . W^T + bias)) + the resized deferred laterals `lats` (one or two Operands), in one GEMM launch."""
+    B, Ho, Wo = geom
+    N, K = W.shape[0], W.shape[1]
+    a = [(P(op.raw), P(op.sc), P(op.sh), op.act, op.geom[1], op.geom[2]) for op in lats] + [(None, None, None, 0, 0, 0)] * (2 - len(lats))
+    for op in lats:
+        if ld(op.raw) != N:
+            raise KDError("FPN laterals must be dense [M, C] matrices")
+    e0 = _prof_begin()
+    lib.call("kd_pwconv_gemm_fpn_sum", P(A), ld(A), P(W), P(bias), P(bnc0.scale), P(bnc0.shift), act0, *a[0], *a[1], P(out), B, Ho, Wo,
+             K, N, stream())
+    M = B * Ho * Wo
+    _prof_end(e0, "pw_gemm", 2.0 * M * N * K, 4.0 * (M * K + M * N + N * K + sum(op.M * N for op in lats)), None, M)
+
+
 def l1_fwd(op: Operand, W, C_out, *, bias, epi, partial, partial_rows=0, m_dev=None):
     """LiDAR layer 1 forward over a virtual layer-0 operand (pts -> layer 0 -> BN+act recomputed on load)."""
     pts, w0, b0 = op.virt

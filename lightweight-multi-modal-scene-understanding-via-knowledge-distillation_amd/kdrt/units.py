@@ -695,6 +695,29 @@ def run_chain_pair(x, units_a: Sequence[UnitSpec], units_b: Sequence[UnitSpec], 
 
 
 # =================================================================================================
+# FPN_BWD_PAIR: 0 one kd_bilinear_bwd launch per lateral, 1 (default) laterals of one geometry below the output size share a
+# kd_bilinear_bwd2 launch (the same bits; profiles/fpn_lateral_sum_ab.txt).
+FPN_BWD_PAIR = [1]
+
+
+# FPN_LATERAL_SUM: 0 (default) never, 1 in inference the output-size lateral's GEMM adds the resized smaller laterals in its epilogue
+# (kd_pwconv_gemm_fpn_sum: the bits of the raw GEMM + kd_bilinear_sum_fwd).  Off: measured inside the KD step at 256 frames the one
+# launch takes 522 us against 147 + 262 us for the GEMM and the quad-body sum kernel (profiles/fpn_lateral_sum_ab.txt).
+FPN_LATERAL_SUM = [0]
+
+
+def fpn_lateral_sum_ok(laterals, lat_in, out_hw) -> bool:
+    """Lateral 0 at the output size on a dense materialised input, one or two more laterals, split arithmetic, a covered shape."""
+    if FPN_LATERAL_SUM[0] == 0 or len(laterals) not in (2, 3) or any(u.kind != "pw" for u in laterals):
+        return False
+    x0, w0 = lat_in[0], laterals[0].conv.weight
+    if (x0.geom[1], x0.geom[2]) != tuple(out_hw) or x0.bnc is not None or ops.get_gemm_arithmetic() != "split":
+        return False
+    if x0.C != w0.shape[1] or any(u.conv.weight.shape[0] != w0.shape[0] for u in laterals) or any(x.geom[0] != x0.geom[0] for x in lat_in):
+        return False
+    return bool(lib.kd_pwconv_gemm_fpn_sum_supported(x0.M, w0.shape[1], w0.shape[0], len(laterals) - 1))
+
+
 class FPNFn(torch.autograd.Function):
     """CameraFPNLite.forward (fusion_module.py:51-64): laterals (Conv1x1) -> bilinear resize to the
     largest stage -> running sum -> DWSeparableConv post block."""
@@ -703,17 +726,23 @@ class FPNFn(torch.autograd.Function):
     def forward(ctx, n_stage, laterals, post_units, training, target_size, *tensors):
         infer, training = training == 2, training == 1
         feats = tensors[:n_stage]
-        lat_ops, lat_recs, in_geoms = [], [], []
-        for f, u in zip(feats, laterals):
-            xm, geom = ops.nhwc_view(f)
-            op, rec = unit_forward(u, Operand(xm, geom), training)
-            lat_ops.append(op); lat_recs.append(rec); in_geoms.append(geom)
+        lat_in = [Operand(*ops.nhwc_view(f)) for f in feats]
+        in_geoms = [x.geom for x in lat_in]
         B = in_geoms[0][0]
         Ho, Wo = target_size if target_size is not None else max(((g[1], g[2]) for g in in_geoms), key=lambda hw: hw[0] * hw[1])
-        Ct = lat_ops[0].C
-        dev = lat_ops[0].raw.device
+        # inference: the smaller laterals first, then the output-size lateral's GEMM writes the sum itself (its raw map is never stored)
+        sum_in_gemm = infer and fpn_lateral_sum_ok(laterals, lat_in, (Ho, Wo))
+        lat_ops, lat_recs = [None] * n_stage, [None] * n_stage
+        for i in range(1 if sum_in_gemm else 0, n_stage):
+            lat_ops[i], lat_recs[i] = unit_forward(laterals[i], lat_in[i], training)
+        Ct = laterals[0].conv.weight.shape[0]
+        dev = lat_in[0].raw.device
         fused = torch.empty(B * Ho * Wo, Ct, device=dev, dtype=torch.float32)
-        if len(lat_ops) <= 3:        # the whole sum in one pass (same bits as accumulating lateral by lateral)
+        if sum_in_gemm:
+            u0 = laterals[0]
+            b0 = _coeffs(u0, None, 0, Ct, B * Ho * Wo, False, None, dev)
+            ops.pw_gemm_fpn_sum(lat_in[0].raw, u0.conv.weight, u0.conv.bias, b0, u0.act, lat_ops[1:], fused, (B, Ho, Wo))
+        elif len(lat_ops) <= 3:        # the whole sum in one pass (same bits as accumulating lateral by lateral)
             a = [(P(op.raw), P(op.sc), P(op.sh), op.act, op.geom[1], op.geom[2]) for op in lat_ops] + [(None, None, None, 0, 0, 0)] * (3 - len(lat_ops))
             lib.call("kd_bilinear_sum_fwd", *a[0], *a[1], *a[2], P(fused), B, Ho, Wo, Ct, stream())
         else:
@@ -754,15 +783,39 @@ class FPNFn(torch.autograd.Function):
         n = ctx.n_stage
         order = sorted(range(n), key=lambda k: 0 if k in ctx.res_src else 1)       # residual sources first: their gradient is an addend
         gmat, pgs = [None] * n, [None] * n
-        for i in order:
+        # The resize adjoint of a lateral reads dfused and that lateral's own forward tensors only -- never another lateral's
+        # gradient -- so two smaller laterals of one geometry take theirs from ONE launch (dfused read once) when the first of
+        # them comes up in `order`; the second finds its (gin, partial) waiting.  `order` / `res_src` below are untouched.
+        adj = {}
+
+        def lat_args(op):
+            return (P(op.raw), P(op.sc), P(op.sh), op.act, P(op.bnc.mean), P(op.bnc.invstd))
+
+        def lat_bufs(op):
+            rows = lib.kd_rowwise_stat_rows(op.M, op.C)
+            return (torch.empty(op.M, op.C, device=dm.device, dtype=torch.float32),
+                    torch.empty(rows * 2 * op.C, device=dm.device, dtype=torch.float32))
+
+        for pos, i in enumerate(order):
             op, rec = ctx.lat_ops[i], ctx.lat_recs[i]
             _, Hi, Wi = op.geom
             C = op.C
             rows = lib.kd_rowwise_stat_rows(op.M, C)
-            gin = torch.empty(op.M, C, device=dm.device, dtype=torch.float32)
-            partial = torch.empty(rows * 2 * C, device=dm.device, dtype=torch.float32)
-            lib.call("kd_bilinear_bwd", P(dfused), P(op.raw), P(op.sc), P(op.sh), op.act, P(op.bnc.mean),
-                     P(op.bnc.invstd), P(gin), P(partial), B, Hi, Wi, Ho, Wo, C, stream())
+            if i in adj:
+                gin, partial = adj.pop(i)
+            else:
+                gin, partial = lat_bufs(op)
+                mate = None
+                # (a mate may be a residual source of this lateral's addend chain, as stage 5's is of stage 4's: only the resize
+                # adjoint is shared, which reads no lateral's gradient; unit_backward below still runs in `order`, one lateral at a time)
+                if FPN_BWD_PAIR[0] and (Hi, Wi) != (Ho, Wo):
+                    mate = next((j for j in order[pos + 1:] if j not in adj and ctx.lat_ops[j].geom == op.geom and ctx.lat_ops[j].C == C), None)
+                if mate is None:
+                    lib.call("kd_bilinear_bwd", P(dfused), *lat_args(op), P(gin), P(partial), B, Hi, Wi, Ho, Wo, C, stream())
+                else:
+                    adj[mate] = lat_bufs(ctx.lat_ops[mate])
+                    lib.call("kd_bilinear_bwd2", P(dfused), *lat_args(op), P(gin), P(partial), *lat_args(ctx.lat_ops[mate]),
+                             P(adj[mate][0]), P(adj[mate][1]), B, Hi, Wi, Ho, Wo, C, stream())
             need = ctx.needs_input_grad[5 + i]
             src = ctx.res_src[i]
             fold = need and src is not None and gmat[src] is not None
