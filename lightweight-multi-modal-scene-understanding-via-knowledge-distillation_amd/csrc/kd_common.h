@@ -30,6 +30,10 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 void kd_set_error(const char* fmt, ...);
 int kd_check_launch(const char* what);
+// dst[0 .. bytes) <- the byte `value`, by a kernel on `stream` (kd_runtime.hip).  Entry points that a training step calls zero their
+// buffers with this and not with hipMemsetAsync: inside a captured hipGraph the memset node filled its destination correctly on
+// the first replay only, and from the second on with 16 bytes of stale launch data ("What survives a step").
+hipError_t kd_fill_async(void* dst, int value, size_t bytes, hipStream_t stream);
 
 #define KD_REQUIRE(cond, code, ...)        \
   do {                                     \

@@ -1040,7 +1040,7 @@ int kd_lidar_l2_fwd_scatter(const float* A, int64_t lda, const float* sc1, const
   KD_REQUIRE(act2 == KD_ACT_RELU || act2 == KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_l2_fwd_scatter: needs a non-negative activation");
   KD_REQUIRE(kd_aligned16(A) && kd_aligned16(W2) && kd_aligned16(sc1) && kd_aligned16(sh1), KD_ERR_ALIGN, "kd_lidar_l2_fwd_scatter: 16-byte alignment");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(grid, 0, (size_t)ncells * N * sizeof(float), st);
+  hipError_t e = kd_fill_async(grid, 0, (size_t)ncells * N * sizeof(float), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_l2_fwd_scatter: memset failed: %s", hipGetErrorString(e));
   GemmArgs g{A, lda, nullptr, 0, sc1, sh1, nullptr, nullptr, nullptr, 1, act1, W2, bias2, grid, N, nullptr, 0,
              reinterpret_cast<const float*>(cell_idx), 0, sc2, sh2, nullptr, nullptr, act2, nullptr, (int)M, K, N, m_dev,

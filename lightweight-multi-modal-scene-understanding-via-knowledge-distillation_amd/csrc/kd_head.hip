@@ -307,7 +307,7 @@ int kd_cls3x3_bwd(const float* dlog_nchw, const float* x, const float* sc, const
   const KdCgLayout l = kd_cg_layout(npix, Cin, 256);
   const int per = NC * Cin * 9 + 4;
   KD_REQUIRE(ws_bytes >= (size_t)l.grid * per * sizeof(float), KD_ERR_WORKSPACE, "kd_cls3x3_bwd: workspace too small");
-  hipError_t e = hipMemsetAsync(ws, 0, (size_t)l.grid * per * sizeof(float), st);
+  hipError_t e = kd_fill_async(ws, 0, (size_t)l.grid * per * sizeof(float), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_cls3x3_bwd: memset failed");
   C3Args a{x, sc, sh, act, w, nullptr, nullptr, dlog_nchw, nullptr, nullptr, nullptr, nullptr, (float*)ws, B, H, W, Cin, NC, l.groups, l.slots};
   hipLaunchKernelGGL(cls3x3_bwd_weight_kernel, dim3(l.grid), dim3(256), 0, st, a);

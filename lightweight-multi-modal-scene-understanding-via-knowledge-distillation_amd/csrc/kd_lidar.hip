@@ -279,7 +279,7 @@ int kd_lidar_scatter_max_fwd(const float* pts, const float* y, const float* sc, 
   KD_REQUIRE(pts && y && sc && sh && grid && B > 0 && N > 0 && C % 4 == 0 && C <= 1024, KD_ERR_ARG, "kd_lidar_scatter_max_fwd: bad args");
   KD_REQUIRE(act == KD_ACT_RELU || act == KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_scatter_max_fwd: needs a non-negative activation");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(grid, 0, (size_t)B * H * W * C * sizeof(float), st);
+  hipError_t e = kd_fill_async(grid, 0, (size_t)B * H * W * C * sizeof(float), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_scatter_max_fwd: memset failed: %s", hipGetErrorString(e));
   const KdCgLayout l = kd_cg_layout((int64_t)B * N, C, 4096);
   ScatArgs a{pts, y, sc, sh, act, grid, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, C,
@@ -301,7 +301,7 @@ int kd_lidar_scatter_max_bwd(const float* pts, const float* y, const float* sc, 
   const size_t need = (size_t)B * H * W * C * sizeof(unsigned);
   KD_REQUIRE(ws_bytes >= need, KD_ERR_WORKSPACE, "kd_lidar_scatter_max_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ws, 0, need, st);
+  hipError_t e = kd_fill_async(ws, 0, need, st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_scatter_max_bwd: memset failed: %s", hipGetErrorString(e));
   const KdCgLayout l = kd_cg_layout((int64_t)B * N, C, 4096);
   ScatArgs a{pts, y, sc, sh, act, const_cast<float*>(grid), (unsigned*)ws, dout, mean, invstd, G, partial, B, N, C,
@@ -365,7 +365,7 @@ int kd_lidar_compact(const float* pts, float* out_pts, int* out_cell, int* count
                      float x0, float x1, float y0, float y1, void* stream) {
   KD_REQUIRE(pts && out_pts && out_cell && counter && B > 0 && N > 0, KD_ERR_ARG, "kd_lidar_compact: bad args");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(counter, 0, sizeof(int), st);
+  hipError_t e = kd_fill_async(counter, 0, sizeof(int), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_compact: memset failed: %s", hipGetErrorString(e));
   const int64_t P = (int64_t)B * N;
   hipLaunchKernelGGL(lidar_compact_kernel, dim3((unsigned)((P + 1023) / 1024)), dim3(1024), 0, st, pts, out_pts, out_cell,
@@ -405,7 +405,7 @@ int kd_lidar_scatter_max_idx_fwd(const float* y, const float* sc, const float* s
   KD_REQUIRE(y && sc && sh && cell_idx && grid && P >= 0 && C % 4 == 0 && C <= 1024 && ncells > 0, KD_ERR_ARG, "kd_lidar_scatter_max_idx_fwd: bad args");
   KD_REQUIRE(act == KD_ACT_RELU || act == KD_ACT_RELU6, KD_ERR_ARG, "kd_lidar_scatter_max_idx_fwd: needs a non-negative activation");
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(grid, 0, (size_t)ncells * C * sizeof(float), st);
+  hipError_t e = kd_fill_async(grid, 0, (size_t)ncells * C * sizeof(float), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_scatter_max_idx_fwd: memset failed: %s", hipGetErrorString(e));
   if (P == 0) return KD_OK;
   const KdCgLayout l = kd_cg_layout(P, C, 4096);
@@ -1240,7 +1240,7 @@ int kd_lidar_cell_sort(const float* pts, int B, int64_t N, int H, int W, float x
   int* rank = (int*)ws;
   int* bsum = rank + P;
   const int nb = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
-  hipError_t e = hipMemsetAsync(seg_start, 0, (size_t)n * sizeof(int), st);
+  hipError_t e = kd_fill_async(seg_start, 0, (size_t)n * sizeof(int), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_cell_sort: memset failed: %s", hipGetErrorString(e));
   const BevGeom g{x0, x1 - x0, y0, y1 - y0, H, W};
   hipLaunchKernelGGL(seg_count_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, pts, row_of_point, rank, seg_start, P, N, g);
@@ -1329,7 +1329,7 @@ int kd_lidar_sort_points_wide(const float* pts, int B, int64_t N, int H, int W, 
   int* bsum = inv + B;
   const int nsb = (int)((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
   const BevGeom g{x0, x1 - x0, y0, y1 - y0, H, W};
-  hipError_t e = hipMemsetAsync(seg_start, 0, (size_t)n * sizeof(int), st);
+  hipError_t e = kd_fill_async(seg_start, 0, (size_t)n * sizeof(int), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "kd_lidar_sort_points_wide: memset failed: %s", hipGetErrorString(e));
   const dim3 blocks((unsigned)(B * nblk)), per_point((unsigned)((P + 255) / 256));
   hipLaunchKernelGGL(wide_count_kernel<0>, blocks, dim3(SORT_BLK), (size_t)nd0 * sizeof(int), st, pts, cell, lrank, T0, seg_start, N, nblk, g);

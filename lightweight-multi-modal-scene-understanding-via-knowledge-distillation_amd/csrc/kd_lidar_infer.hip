@@ -236,7 +236,7 @@ static int li_launch(int np, const char* who, const float* pts, const int* cell,
   KD_REQUIRE(P < (int64_t)1 << 31, KD_ERR_SHAPE, "%s: too many points", who);
   KD_REQUIRE(kd_aligned16(pts) && kd_aligned16(w0) && kd_aligned16(W1) && kd_aligned16(W2), KD_ERR_ALIGN, "%s: 16-byte alignment", who);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(grid, 0, (size_t)ncells * N2 * sizeof(float), st);
+  hipError_t e = kd_fill_async(grid, 0, (size_t)ncells * N2 * sizeof(float), st);
   KD_REQUIRE(e == hipSuccess, (int)e, "%s: memset failed: %s", who, hipGetErrorString(e));
   const int64_t nslab = (P + 31) / 32, want = (nslab + IW - 1) / IW;
   LiArgs g{pts, cell, p_dev, w0, b0, sc0, sh0, W1, bias1, sc1, sh1, W2, bias2, sc2, sh2, grid, (int)P};

@@ -23,6 +23,34 @@ int kd_check_launch(const char* what) {
 }
 
 namespace {
+// 16-byte stores over the aligned body (a block owns 1024 consecutive chunks per sweep, four stores in flight per thread), single
+// bytes for what is left (and for a destination that is not 16-byte aligned)
+__global__ __launch_bounds__(256) void fill_kernel(unsigned char* __restrict__ dst, uint32_t word, size_t n16, size_t bytes) {
+  uint4* d = reinterpret_cast<uint4*>(dst);
+  const uint4 v = make_uint4(word, word, word, word);
+  for (size_t base = (size_t)blockIdx.x * 1024; base < n16; base += (size_t)gridDim.x * 1024) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const size_t i = base + (size_t)j * 256 + threadIdx.x;
+      if (i < n16) d[i] = v;
+    }
+  }
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
+  for (size_t i = n16 * 16 + t; i < bytes; i += step) dst[i] = (unsigned char)word;
+}
+}  // namespace
+
+hipError_t kd_fill_async(void* dst, int value, size_t bytes, hipStream_t stream) {
+  if (!dst || bytes == 0) return bytes == 0 ? hipSuccess : hipErrorInvalidValue;
+  const uint32_t word = 0x01010101u * (uint32_t)(value & 0xff);
+  const size_t n16 = kd_aligned16(dst) ? bytes / 16 : 0;
+  const size_t tail = bytes - n16 * 16;
+  const size_t blocks = (n16 + 1023) / 1024 > (tail + 255) / 256 ? (n16 + 1023) / 1024 : (tail + 255) / 256;
+  hipLaunchKernelGGL(fill_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, stream, (unsigned char*)dst, word, n16, bytes);
+  return hipGetLastError();
+}
+
+namespace {
 // out[i] = sum_k slab[k][i].  The split dimension is walked by 16 lanes in parallel (lane y adds rows y, y + 16, ... in order)
 // and the 16 partial sums are combined through LDS in lane order: deterministic, and the same order for both forms below.
 // Round 4: where n is a multiple of 4 (every weight matrix) a thread owns FOUR consecutive elements (16-byte loads, four rows in

@@ -176,6 +176,7 @@ class GraphedKDStep:
         mode = {} if step.reducer is None else {"capture_error_mode": "thread_local"}
         with torch.cuda.graph(self.graph, **mode):
             self.out = self._body()
+        self.transposes = ops.TRANSPOSES.hold()     # the captured W^T refresh reads this table: it lives as long as the graph
         self.replays = 0
 
     def _micro_batches(self):

@@ -424,6 +424,13 @@ class TransposeCache:
         for e in ents:
             e[2] = self._stamp(e)
 
+    def hold(self):
+        """Everything a captured refresh launch reads and writes by raw pointer: the table and every registered weight view and
+        W^T buffer.  A captured graph keeps the returned object for its own lifetime: the cache drops its table whenever another
+        model registers a weight, and its entries when their model is gone, and a replay must not find that memory handed to
+        somebody else."""
+        return (self.table, [(e[0], e[1]) for e in self.entries.values()])
+
     def clear(self):
         self.entries.clear()
         self.table = None

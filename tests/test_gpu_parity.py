@@ -203,7 +203,7 @@ def test_kd_step_vs_oracle_and_adamw():
 def _fp64_table():
     """{"kd/weighted": [seeds], ...}: input seeds whose batch kept every pre-activation clear of a ReLU / ReLU6 / max kink in
     EVERY evaluation (CPU fp32 oracle, GPU in both GEMM arithmetics, streaming mode 0 / 1 / 2) when tools/diag_fp64_seeds.py
-    scanned them on an MI355X (scan output in profiles/r03_fp64_seed_scan.txt, list in tests/golden/fp64_clean_seeds.json)."""
+    scanned them on an MI355X (scan output in profiles/fp64_seed_scan.txt, list in tests/golden/fp64_clean_seeds.json)."""
     import json
     import os
     return json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fp64_clean_seeds.json")))["clean"]

@@ -53,6 +53,15 @@ def test_trainer_ce_runs_and_checkpoints(tmp_path):
     a, _ = tr.train_epoch()
     b, _ = tr2.train_epoch()
     assert abs(a - b) < 1e-5                                           # identical continuation
+    # ... bit for bit: parameters, gradients, moments, device counters and every module buffer after the resumed epoch
+    bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t
+    for name in ("data", "grad"):
+        assert torch.equal(bits(getattr(tr.optimizer.flat, name)), bits(getattr(tr2.optimizer.flat, name))), name
+    for name in ("exp_avg", "exp_avg_sq", "dev_state"):
+        assert torch.equal(bits(getattr(tr.optimizer, name)), bits(getattr(tr2.optimizer, name))), name
+    assert tr.optimizer._step == tr2.optimizer._step == 12
+    for (n1, b1), (_, b2) in zip(model.named_buffers(), model2.named_buffers()):
+        assert torch.equal(bits(b1), bits(b2)), n1
 
 
 def test_kd_trainer_runs(tmp_path):
