@@ -422,6 +422,29 @@ int kd_semantic_remap(const int64_t* raw, int64_t n, uint64_t remap_bits, int64_
 /* The multi-class remap: out[i] = table[raw[i]] for 0 <= raw[i] < ntab, else 0 (background); table: device int64 [ntab], ntab >= 1;
  * raw and out are two buffers.  Followed by kd_bev_rasterize with remap = 0 it gives a BEV mask of class indices. */
 int kd_semantic_remap_table(const int64_t* raw, int64_t n, const int64_t* table, int ntab, int64_t* out, void* stream);
+/* The voting rasteriser for class maps: kd_bev_rasterize decides a cell by the sweep's point order, this one by counts.  Points,
+ * offsets, range test and cell arithmetic are those of kd_bev_rasterize (the same device functions: a point's cell is the same bit
+ * for bit).  cls: class indices as kd_semantic_remap_table writes them; NC in 2..16, else KD_ERR_SHAPE and nothing is written.
+ * rule: 1 = majority, 2 = priority, anything else KD_ERR_ARG (the first-point rule is kd_bev_rasterize).  rank: device int32 [NC],
+ * or NULL for all zero; rank[0] is ignored.  min_points >= 1.  votes: optional int32 [B, H, W].
+ * For every cell, n_c = the number of points of the frame that pass the inclusive range test, fall into the cell and have class c,
+ * 1 <= c < NC.  A point of class 0, of a negative class or of a class >= NC counts nowhere; a NaN coordinate fails the range test.
+ * A class is eligible in a cell when n_c >= min_points.
+ *   majority: the eligible class with the largest n_c; equal counts go to the larger rank[c], then to the smaller c.
+ *   priority: the eligible class with the largest rank[c]; equal ranks go to the larger n_c, then to the smaller c.
+ *   no eligible class: mask = 0.      votes = the winner's n_c, 0 in a background cell.
+ * ws: kd_bev_rasterize_vote_ws_bytes(B, H, W, NC) bytes (0 for arguments the call refuses), 16-byte aligned: uint32 counters
+ * [B][H * W][K], K = 4 / 8 / 16, the class bucket that holds NC; cleared inside the call.  B * H * W * K < 2^31, n_total < 2^31.
+ * Integer atomics only: the same input gives the same bits on every call, whatever the order of the points inside a frame.
+ * tests/_label_rule_ref.py is the numpy mirror of the rule. */
+size_t kd_bev_rasterize_vote_ws_bytes(int B, int H, int W, int NC);
+int kd_bev_rasterize_vote(const float* x, const float* y, const int64_t* cls, const int64_t* offsets, int B, int64_t n_total,
+                          int NC, int rule, const int32_t* rank, int min_points, int H, int W,
+                          float x_min, float x_span, float x_max, float y_min, float y_span, float y_max,
+                          void* ws, size_t ws_bytes, int64_t* mask, int32_t* votes, void* stream);
+/* Class histogram of a label mask: counts is int64 [NC + 1] and is ACCUMULATED into: counts[c] += #{mask == c} for 0 <= c < NC,
+ * counts[NC] += every other value (the ignore index -1 lands there).  NC in 1..16, n >= 0 (n = 0: nothing is launched). */
+int kd_label_histogram(const int64_t* mask, int64_t n, int NC, int64_t* counts, void* stream);
 /* out[max_points,4] = stack(x,y,z,i) zero-padded, or (choice != NULL, n >= max_points) the rows choice[0..max_points) */
 int kd_points_prepare(const float* x, const float* y, const float* z, const float* intensity, const int64_t* choice,
                       int64_t n, int64_t max_points, float* out, void* stream);

@@ -3,6 +3,8 @@
 //     each cell takes the label of the FIRST point (input order) whose label is non-zero.  The reference walks
 //     the points in a Python loop; here every labelled point does an atomicMin of its in-frame index on its
 //     cell and a second kernel reads the winner's label: order-independent, bit-exact, one pass over the points.
+//   * the voting rasteriser for class maps (no reference counterpart): majority or priority per cell from per-(cell, class)
+//     integer counters, and the class histogram of a label mask
 //   * point stacking + zero padding / subsample gather (:113-127)
 //   * uint8 HWC image -> float32 CHW / 255 (:108-111)
 //   * the same two for a whole ragged batch in one launch each; a frame longer than max_points is cut to a uniform
@@ -61,6 +63,95 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(RastArgs a) {
     const int b = (int)(k / ((int64_t)a.H * a.W));
     a.mask[k] = f == kEmpty ? 0 : label_of(a.cls[a.off[b] + f], a.remap, a.bits);
   }
+}
+
+// ---- voting rasteriser: majority / priority per cell ---------------------------------------------------------------
+// Count pass: every point that passes the range test and has a class in 1 .. NC-1 adds to the uint32 counter
+// ws[(b * H * W + cell) * K + class], K = the class bucket 4 / 8 / 16 that holds NC, so a cell's counters are one aligned
+// 16 / 32 / 64 byte group.  Real sweeps put thousands of consecutive points into the cells round the sensor: a run of
+// consecutive lanes with the same counter is merged, its first lane adds the run length (one atomic per run).  The slot
+// carries frame, cell and class, so a run ends at a frame boundary; a point that counts nowhere has no slot and ends it too.
+// Against one atomic per point (profiles/label_rule_ab.txt): the same time on a uniform scene, 13 times faster on a concentrated
+// scene in scan order.
+// Resolve pass: one thread per cell reads its K counters with 16-byte loads and picks the winner.  Integer atomics only:
+// the counters, and so every output bit, do not depend on the execution order.
+struct VoteArgs {
+  const float* x; const float* y; const int64_t* cls; const int64_t* off; int B; int64_t n;
+  int NC, rule, min_points, H, W; float x0, xs, x1, y0, ys, y1;
+  const int32_t* rank; uint32_t* cnt; int64_t* mask; int32_t* votes;
+};
+
+constexpr int kRuleMajority = 1, kRulePriority = 2;
+
+template <int K>
+__global__ __launch_bounds__(256) void vote_count_kernel(VoteArgs a) {
+  const int lane = threadIdx.x & 63;
+  // the trip count is the same for the whole block: the shuffle and the ballot below run with all 64 lanes
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < a.n; base += (int64_t)gridDim.x * 256) {
+    const int64_t i = base + threadIdx.x;
+    int slot = -1;                                // no counter: out of range, class 0 / negative / >= NC, or past the end
+    if (i < a.n) {
+      const float x = a.x[i], y = a.y[i];
+      const int64_t c = a.cls[i];
+      const bool keep = x >= a.x0 && x <= a.x1 && y >= a.y0 && y <= a.y1;    // NaN fails every comparison
+      if (keep && c >= 1 && c < a.NC) {
+        const int b = frame_of(a.off, a.B, i);
+        const int cell = axis_cell(y, a.y0, a.ys, a.H) * a.W + axis_cell(x, a.x0, a.xs, a.W);
+        slot = (b * a.H * a.W + cell) * K + (int)c;                          // the host checked B * H * W * K < 2^31
+      }
+    }
+    const int prev = __shfl_up(slot, 1, 64);
+    const bool starts = lane == 0 || prev != slot;
+    const unsigned long long heads = __ballot(starts);
+    if (starts && slot >= 0) {
+      const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+      const unsigned int len = above ? (unsigned int)__ffsll((long long)above) : (unsigned int)(64 - lane);
+      atomicAdd(a.cnt + slot, len);
+    }
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void vote_resolve_kernel(VoteArgs a) {
+  int rk[K];
+#pragma unroll
+  for (int c = 0; c < K; ++c) rk[c] = (a.rank && c >= 1 && c < a.NC) ? a.rank[c] : 0;
+  const int64_t ncell = (int64_t)a.B * a.H * a.W;
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < ncell; k += (int64_t)gridDim.x * 256) {
+    uint32_t n[K];
+    const uint4* src = reinterpret_cast<const uint4*>(a.cnt + k * K);
+#pragma unroll
+    for (int q = 0; q < K / 4; ++q) {
+      const uint4 v = src[q];
+      n[4 * q] = v.x; n[4 * q + 1] = v.y; n[4 * q + 2] = v.z; n[4 * q + 3] = v.w;
+    }
+    int best = 0, brk = 0;
+    uint32_t bn = 0;
+#pragma unroll
+    for (int c = 1; c < K; ++c) {                 // ascending: on a full tie the smaller class stays
+      const bool eligible = c < a.NC && n[c] >= (uint32_t)a.min_points;
+      const bool better = a.rule == kRuleMajority ? (n[c] > bn || (n[c] == bn && rk[c] > brk))
+                                                  : (rk[c] > brk || (rk[c] == brk && n[c] > bn));
+      if (eligible && (best == 0 || better)) { best = c; bn = n[c]; brk = rk[c]; }
+    }
+    a.mask[k] = best;
+    if (a.votes) a.votes[k] = (int32_t)bn;
+  }
+}
+
+// counts[c] += #{mask == c} for 0 <= c < NC, counts[NC] += every other value: 17 LDS counters per block, one 64-bit atomic per
+// non-zero counter (the pattern of confusion16_kernel in kd_loss.hip)
+__global__ __launch_bounds__(256) void label_histogram_kernel(const int64_t* __restrict__ mask, int64_t n, int NC,
+                                                              unsigned long long* counts) {
+  __shared__ unsigned int loc[17];
+  if (threadIdx.x < 17) loc[threadIdx.x] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t v = mask[i];
+    atomicAdd(&loc[(v >= 0 && v < NC) ? (int)v : NC], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x <= NC && loc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)loc[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void remap_kernel(const int64_t* __restrict__ raw, int64_t n, uint64_t bits,
@@ -238,6 +329,8 @@ int grid_for(int64_t n) {
   return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
 }
 
+int vote_bucket(int NC) { return NC <= 4 ? 4 : (NC <= 8 ? 8 : 16); }
+
 }  // namespace
 
 extern "C" {
@@ -260,6 +353,61 @@ int kd_bev_rasterize(const float* x, const float* y, const int64_t* cls, const i
   if (n_total > 0) hipLaunchKernelGGL(raster_claim_kernel, dim3(grid_for(n_total)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(raster_resolve_kernel, dim3(grid_for((int64_t)B * H * W)), dim3(256), 0, st, a);
   return kd_check_launch("kd_bev_rasterize");
+}
+
+size_t kd_bev_rasterize_vote_ws_bytes(int B, int H, int W, int NC) {
+  if (B <= 0 || H <= 0 || W <= 0 || NC < 2 || NC > 16) return 0;
+  return (size_t)B * H * W * vote_bucket(NC) * sizeof(uint32_t);
+}
+
+// The majority / priority rule per cell (include/kd_hip.h carries the specification): memset of the counters, count pass, resolve.
+int kd_bev_rasterize_vote(const float* x, const float* y, const int64_t* cls, const int64_t* offsets, int B, int64_t n_total,
+                          int NC, int rule, const int32_t* rank, int min_points, int H, int W, float x_min, float x_span,
+                          float x_max, float y_min, float y_span, float y_max, void* ws, size_t ws_bytes, int64_t* mask,
+                          int32_t* votes, void* stream) {
+  KD_REQUIRE(NC >= 2 && NC <= 16, KD_ERR_SHAPE, "kd_bev_rasterize_vote: num_classes=%d unsupported (2..16)", NC);
+  KD_REQUIRE(rule == kRuleMajority || rule == kRulePriority, KD_ERR_ARG,
+             "kd_bev_rasterize_vote: rule=%d is neither 1 (majority) nor 2 (priority); the first-point rule is kd_bev_rasterize", rule);
+  KD_REQUIRE(min_points >= 1, KD_ERR_ARG, "kd_bev_rasterize_vote: min_points=%d must be at least 1", min_points);
+  KD_REQUIRE(offsets && mask && ws && B > 0 && H > 0 && W > 0 && n_total >= 0, KD_ERR_ARG, "kd_bev_rasterize_vote: bad args");
+  KD_REQUIRE(n_total == 0 || (x && y && cls), KD_ERR_ARG, "kd_bev_rasterize_vote: null point arrays with n_total=%lld", (long long)n_total);
+  KD_REQUIRE(n_total < (int64_t)1 << 31, KD_ERR_SHAPE, "kd_bev_rasterize_vote: too many points");          // uint32 counters
+  const int K = vote_bucket(NC);
+  KD_REQUIRE((int64_t)B * H * W * K < (int64_t)1 << 31, KD_ERR_SHAPE, "kd_bev_rasterize_vote: B * H * W * %d counters exceed 2^31", K);
+  KD_REQUIRE(x_span > 0.f && y_span > 0.f, KD_ERR_ARG, "kd_bev_rasterize_vote: empty range");
+  KD_REQUIRE(kd_aligned16(ws), KD_ERR_ALIGN, "kd_bev_rasterize_vote: the workspace must be 16-byte aligned");
+  const size_t need = kd_bev_rasterize_vote_ws_bytes(B, H, W, NC);
+  KD_REQUIRE(ws_bytes >= need, KD_ERR_WORKSPACE, "kd_bev_rasterize_vote: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(ws, 0, need, st);
+  KD_REQUIRE(e == hipSuccess, (int)e, "kd_bev_rasterize_vote: memset failed");
+  VoteArgs a{x, y, cls, offsets, B, n_total, NC, rule, min_points, H, W, x_min, x_span, x_max, y_min, y_span, y_max,
+             rank, (uint32_t*)ws, mask, votes};
+  const dim3 gc(grid_for(n_total)), gr(grid_for((int64_t)B * H * W)), blk(256);
+  if (K == 4) {
+    if (n_total > 0) hipLaunchKernelGGL(vote_count_kernel<4>, gc, blk, 0, st, a);
+    hipLaunchKernelGGL(vote_resolve_kernel<4>, gr, blk, 0, st, a);
+  } else if (K == 8) {
+    if (n_total > 0) hipLaunchKernelGGL(vote_count_kernel<8>, gc, blk, 0, st, a);
+    hipLaunchKernelGGL(vote_resolve_kernel<8>, gr, blk, 0, st, a);
+  } else {
+    if (n_total > 0) hipLaunchKernelGGL(vote_count_kernel<16>, gc, blk, 0, st, a);
+    hipLaunchKernelGGL(vote_resolve_kernel<16>, gr, blk, 0, st, a);
+  }
+  return kd_check_launch("kd_bev_rasterize_vote");
+}
+
+// counts[NC + 1] (int64, ACCUMULATED into): the class histogram of a label mask; values outside 0 .. NC-1 (the ignore index) -> counts[NC]
+int kd_label_histogram(const int64_t* mask, int64_t n, int NC, int64_t* counts, void* stream) {
+  KD_REQUIRE(NC >= 1 && NC <= 16, KD_ERR_SHAPE, "kd_label_histogram: num_classes=%d unsupported (1..16)", NC);
+  KD_REQUIRE(counts && n >= 0 && (n == 0 || mask), KD_ERR_ARG, "kd_label_histogram: bad args");
+  KD_REQUIRE(n < (int64_t)1 << 40, KD_ERR_SHAPE, "kd_label_histogram: too many labels");                  // uint32 counters per block
+  if (n == 0) return KD_OK;
+  int64_t grid = (n + 255) / 256;
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(label_histogram_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, mask, n, NC,
+                     (unsigned long long*)counts);
+  return kd_check_launch("kd_label_histogram");
 }
 
 int kd_semantic_remap(const int64_t* raw, int64_t n, uint64_t remap_bits, int64_t* out, void* stream) {

@@ -576,3 +576,23 @@ def confusion(logits, target, num_classes: int = 2, ignore_index: int = -1, out:
     entry = "kd_argmax_confusion" if NC <= 4 and M <= 4 else "kd_argmax_confusion16"
     lib.call(entry, P(z), P(target.contiguous()), int(ignore_index), P(out), P(pred), B, NC, M, H * W, stream())
     return out, pred
+
+
+def class_weights_from_counts(counts, scheme: str = "median_freq"):
+    """Class weights for the weighted cross-entropy from a class histogram of the labels (PandaSetDataset.label_counts), as a list
+    of Python floats, computed in float64 on the host.  `median_freq` (median frequency balancing): f_c = counts[c] / sum(counts),
+    w_c = median{f_k : counts[k] > 0} / f_c; a class that never occurs gets weight 0.  All-zero, negative or non-integer counts and
+    an unknown scheme are a ValueError."""
+    if scheme != "median_freq":
+        raise ValueError(f"class_weights_from_counts: scheme must be 'median_freq', got {scheme!r}")
+    c = np.asarray(counts)
+    if c.ndim != 1 or c.size == 0 or not (np.issubdtype(c.dtype, np.integer) or np.issubdtype(c.dtype, np.floating)):
+        raise ValueError("class_weights_from_counts: counts must be a non-empty 1-D sequence of numbers")
+    c = c.astype(np.float64)
+    if not np.all(np.isfinite(c)) or np.any(c < 0) or np.any(c != np.floor(c)):
+        raise ValueError("class_weights_from_counts: counts must be non-negative whole numbers")
+    if c.sum() <= 0:
+        raise ValueError("class_weights_from_counts: every count is zero")
+    f = c / c.sum()
+    med = np.median(f[c > 0])
+    return [float(med / v) if v > 0 else 0.0 for v in f]

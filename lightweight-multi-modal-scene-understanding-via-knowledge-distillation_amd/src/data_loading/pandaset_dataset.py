@@ -23,6 +23,10 @@ jitter, intensity gain) ahead of the rasteriser and the point stacker, so BEV la
 and kd_image_augment_batch adjusts the float32 image batch (gains, offset, clamp, the flip's mirror, camera dropout).
 Every frame's transform is a function of (`sample_seed`, epoch, dataset index) alone.
 
+`label_rule=LabelRule(...)` (opt-in, default off, with a `class_map` only): a BEV cell takes the majority or the highest-priority
+class of its points (kd_bev_rasterize_vote) and not the class of its first labelled point in sweep order; `label_counts()` and
+kdrt.losses.class_weights_from_counts turn the rasterised labels into class weights.
+
 `SyntheticPandaSet` serves frames of the same contract when there is no dataset on disk:
     image        float32 [3, 256, 256] in [0, 1]
     points       float32 [max_points, 4]  (x, y, z, intensity), zero-padded tail
@@ -31,6 +35,7 @@ Every frame's transform is a function of (`sample_seed`, epoch, dataset index) a
 import gc
 import os
 from collections import deque
+from dataclasses import dataclass
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -62,9 +67,28 @@ def _f32(v) -> float:
     return float(np.float32(v))
 
 
+def _vote_launch(rule: "LabelRule", rank_dev, num_classes: int, x, y, lab, off, B: int, n: int, H: int, W: int, pc_range, ws,
+                 nbytes: int, mask, votes, s: int):
+    """kd_bev_rasterize_vote on stream `s`: the cell rule of `rule` over class indices (`rank_dev`: rule.ranks() on the device)."""
+    x0, x1, y0, y1 = pc_range
+    lib.call("kd_bev_rasterize_vote", P(x), P(y), P(lab), P(off), B, n, num_classes, rule.code, P(rank_dev), rule.min_points, H, W,
+             _f32(x0), _f32(x1 - x0), _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws), nbytes, P(mask), P(votes), s)
+
+
 def rasterize_bev_batch(xs: Sequence, ys: Sequence, classes: Sequence, grid_size=(64, 64), pc_range=(-50, 50, -50, 50),
-                        remap: bool = False) -> torch.Tensor:
-    """B ragged frames in one launch -> int64 [B, H, W] on the device.  remap=True applies remap_semantic first."""
+                        remap: bool = False, rule: "LabelRule" = None, num_classes: int = None, want_votes: bool = False):
+    """B ragged frames in one launch -> int64 [B, H, W] on the device.  remap=True applies remap_semantic first.
+    `rule` (a LabelRule; None: the first labelled point of a cell wins, the call as it always was): majority or priority per cell
+    over class indices in [0, num_classes - 1] -- it needs remap=False and `num_classes`.  want_votes=True (with a rule) also
+    returns the winner's point count per cell, int32 [B, H, W]."""
+    if rule is not None:
+        if not isinstance(rule, LabelRule):
+            raise ValueError(f"rule must be a LabelRule or None, got {type(rule).__name__}")
+        if remap or num_classes is None:
+            raise ValueError("a label rule votes over class indices: it needs remap=False and num_classes")
+        rank = rule.ranks(num_classes)                     # validates num_classes and the ranks' classes (ValueError)
+    elif want_votes:
+        raise ValueError("want_votes needs a label rule: the first-point rule counts nothing")
     B = len(xs)
     if B == 0:
         raise KDError("rasterize_bev_batch needs at least one frame")
@@ -78,6 +102,12 @@ def rasterize_bev_batch(xs: Sequence, ys: Sequence, classes: Sequence, grid_size
     H, W = int(grid_size[0]), int(grid_size[1])
     x0, x1, y0, y1 = pc_range
     mask = torch.empty(B, H, W, dtype=torch.int64, device="cuda")
+    if rule is not None:
+        votes = torch.empty(B, H, W, dtype=torch.int32, device="cuda") if want_votes else None
+        nbytes = lib.kd_bev_rasterize_vote_ws_bytes(B, H, W, num_classes)
+        _vote_launch(rule, torch.from_numpy(rank).cuda(), num_classes, x, y, c, off, B, x.numel(), H, W, pc_range,
+                     workspace(nbytes, mask.device), nbytes, mask, votes, stream())
+        return (mask, votes) if want_votes else mask
     nbytes = lib.kd_bev_rasterize_ws_bytes(B, H, W)
     ws = workspace(nbytes, mask.device)
     lib.call("kd_bev_rasterize", P(x), P(y), P(c), P(off), B, x.numel(), 1 if remap else 0, _DRIVABLE_BITS, H, W,
@@ -124,6 +154,76 @@ def class_map_table(class_map) -> np.ndarray:
     for k, v in items:
         table[k] = v
     return table
+
+
+_RULE_CODES = {"majority": 1, "priority": 2}           # the `rule` argument of kd_bev_rasterize_vote
+
+
+def _rank_int(v, what: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"LabelRule: {what} must be an integer, got {v!r}")
+    v = int(v)
+    if not -(1 << 31) <= v < (1 << 31):
+        raise ValueError(f"LabelRule: {what} {v} outside int32")
+    return v
+
+
+@dataclass(frozen=True)
+class LabelRule:
+    """How a BEV cell with points of several classes gets its label (kd_bev_rasterize_vote; classes are the indices of a class map,
+    0 = background, which never votes).  A class is eligible in a cell with at least `min_points` points there.
+    kind="majority": the eligible class with the most points; equal counts go to the higher rank, then to the lower class index.
+    kind="priority": the eligible class of the highest rank; equal ranks go to the larger count, then to the lower class index.
+    `priority`: None (every rank 0), a sequence of one integer rank per class (index 0 is ignored), or a dict {class: rank} whose
+    unnamed classes have rank 0.  Validated here (ValueError); that the classes lie inside a map's range is checked where the map is
+    known (`ranks`, the dataset's constructor).  Without a rule a cell takes the class of its first labelled point in input order."""
+    kind: str = "majority"
+    priority: object = None
+    min_points: int = 1
+
+    def __post_init__(self):
+        if self.kind not in _RULE_CODES:
+            raise ValueError(f"LabelRule: kind must be 'majority' or 'priority', got {self.kind!r}")
+        if isinstance(self.min_points, bool) or not isinstance(self.min_points, (int, np.integer)) or not 1 <= self.min_points < (1 << 31):
+            raise ValueError(f"LabelRule: min_points must be an integer >= 1, got {self.min_points!r}")
+        object.__setattr__(self, "min_points", int(self.min_points))
+        pr = self.priority
+        if pr is None:
+            return
+        if isinstance(pr, dict):
+            items = tuple(sorted((_rank_int(k, "a class index"), _rank_int(v, f"the rank of class {k}")) for k, v in pr.items()))
+            for c, _ in items:
+                if not 0 <= c < MAX_CLASSES:
+                    raise ValueError(f"LabelRule: class index {c} outside [0, {MAX_CLASSES - 1}]")
+            object.__setattr__(self, "priority", dict(items))
+        elif isinstance(pr, (list, tuple, np.ndarray)) and np.ndim(pr) == 1:
+            ranks = tuple(_rank_int(v, f"the rank of class {c}") for c, v in enumerate(list(pr)))
+            if not 2 <= len(ranks) <= MAX_CLASSES:
+                raise ValueError(f"LabelRule: a priority sequence has one rank per class, 2 to {MAX_CLASSES}; got {len(ranks)}")
+            object.__setattr__(self, "priority", ranks)
+        else:
+            raise ValueError(f"LabelRule: priority must be None, a sequence of ranks or a dict {{class: rank}}, got {type(pr).__name__}")
+
+    @property
+    def code(self) -> int:
+        return _RULE_CODES[self.kind]
+
+    def ranks(self, num_classes: int) -> np.ndarray:
+        """int32 [num_classes]: the `rank` array of kd_bev_rasterize_vote.  ValueError when the rule does not fit `num_classes`
+        classes: a sequence of another length, a dict that names a class outside [0, num_classes - 1]."""
+        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or not 2 <= num_classes <= MAX_CLASSES:
+            raise ValueError(f"LabelRule: num_classes must be an integer in [2, {MAX_CLASSES}], got {num_classes!r}")
+        out = np.zeros(int(num_classes), np.int32)
+        if isinstance(self.priority, dict):
+            for c, r in self.priority.items():
+                if c >= num_classes:
+                    raise ValueError(f"LabelRule: priority names class {c}, the class map has classes 0..{num_classes - 1}")
+                out[c] = r
+        elif self.priority is not None:
+            if len(self.priority) != num_classes:
+                raise ValueError(f"LabelRule: priority has {len(self.priority)} ranks, the class map has {num_classes} classes")
+            out[:] = self.priority
+        return out
 
 
 def remap_semantic_table(raw_ids, table, s: int = None):
@@ -263,15 +363,18 @@ class StagingSet:
 class PandaSetDataset(Dataset):
     """2-class version: background (0) and drivable (1, includes lanes).  `class_map` (a dict or sequence raw id -> class index
     in [0, NC-1], 0 = background; see class_map_table): the multi-class version -- every prepare path then runs the table remap as
-    one extra launch and rasterises the class indices (first point in input order with a non-zero class wins, as before)."""
+    one extra launch and rasterises the class indices (first point in input order with a non-zero class wins, as before).
+    `label_rule` (a LabelRule; needs a class map): the cell takes the majority or the highest-priority class of its points -- the
+    rasteriser launch of every prepare path is then kd_bev_rasterize_vote, after the same table remap."""
 
     def __init__(self, root: str, scene_ids: List[str], image_size: Tuple[int, int] = (256, 256),
                  grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, verbose: bool = True,
-                 device_resize: bool = False, class_map=None):
+                 device_resize: bool = False, label_rule: LabelRule = None, class_map=None):
         self.root, self.scene_ids = root, scene_ids
         self.image_size, self.grid_size, self.max_points = image_size, grid_size, max_points
         self.device_resize = bool(device_resize)
         self.set_class_map(class_map)
+        self.set_label_rule(label_rule)
         self.pc_range = (-50, 50, -50, 50)
         self.samples = self._index_scenes(verbose=verbose)
         if verbose:
@@ -307,8 +410,25 @@ class PandaSetDataset(Dataset):
         self.class_table = None if class_map is None else class_map_table(class_map)
         self._table_dev = None
 
+    label_rule = _rank_dev = None                  # a subclass with its own constructor keeps the first-point rule
+
+    def set_label_rule(self, label_rule):
+        """None: a cell takes the class of its first labelled point (the default).  A LabelRule: majority or priority per cell, on
+        every prepare path; it needs a class map (under the 2-class drivable remap every rule gives the same mask) and is checked
+        against the map's classes here (ValueError)."""
+        if label_rule is not None:
+            if not isinstance(label_rule, LabelRule):
+                raise ValueError(f"label_rule must be a LabelRule or None, got {type(label_rule).__name__}")
+            if self.class_table is None:
+                raise ValueError("label_rule needs a class_map: with the 2-class drivable labels every rule gives the same mask")
+            label_rule.ranks(self._vote_classes())
+        self.label_rule, self._rank_dev = label_rule, None
+
+    def _vote_classes(self) -> int:
+        return max(2, self.num_classes)            # a map of background alone still has the 2 classes the kernel starts at
+
     def __getstate__(self):                        # a pickled copy (spawned DataLoader workers) carries no device tensor
-        return {**self.__dict__, "_table_dev": None}
+        return {**self.__dict__, "_table_dev": None, "_rank_dev": None}
 
     @property
     def num_classes(self) -> int:
@@ -324,6 +444,24 @@ class PandaSetDataset(Dataset):
         out = torch.empty_like(cls)
         lib.call("kd_semantic_remap_table", P(cls), n, P(self._table_dev), self._table_dev.numel(), P(out), s)
         return out, 0
+
+    def _raster_ws_bytes(self, B: int, GH: int, GW: int) -> int:
+        if self.label_rule is None:
+            return lib.kd_bev_rasterize_ws_bytes(B, GH, GW)
+        return lib.kd_bev_rasterize_vote_ws_bytes(B, GH, GW, self._vote_classes())
+
+    def _rasterize(self, x, y, lab, remap: int, off, B: int, n: int, GH: int, GW: int, ws, nbytes: int, seg, s: int):
+        """The rasteriser launch of the batched prepare paths on stream `s`: kd_bev_rasterize, or -- with a label rule --
+        kd_bev_rasterize_vote over the table-remapped classes (`ws`: at least _raster_ws_bytes(B, GH, GW) bytes)."""
+        x0, x1, y0, y1 = self.pc_range
+        if self.label_rule is None:
+            lib.call("kd_bev_rasterize", P(x), P(y), P(lab), P(off), B, n, remap, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
+                     _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws), nbytes, P(seg), s)
+            return
+        if self._rank_dev is None:                 # copied once, like the table
+            self._rank_dev = torch.from_numpy(self.label_rule.ranks(self._vote_classes())).cuda()
+        _vote_launch(self.label_rule, self._rank_dev, self._vote_classes(), x, y, lab, off, B, n, GH, GW, self.pc_range, ws, nbytes,
+                     seg, None, s)
 
     def load_raw(self, idx: int) -> Dict[str, object]:
         """Host I/O only (safe in DataLoader workers): decoded + resized uint8 image, float32 point columns,
@@ -365,8 +503,9 @@ class PandaSetDataset(Dataset):
                 raise KDError("x, y and labels must have the same length per frame")
             lab, _ = self._labels(raw, raw.numel(), stream())
             bounds = np.concatenate([[0], np.cumsum([int(x.numel()) for x in xs])]).tolist()
+            vote = {} if self.label_rule is None else {"rule": self.label_rule, "num_classes": self._vote_classes()}
             seg = rasterize_bev_batch(xs, ys, [lab[a:b] for a, b in zip(bounds[:-1], bounds[1:])], self.grid_size, self.pc_range,
-                                      remap=False)
+                                      remap=False, **vote)
         pts = torch.stack([prepare_points(x, y, r["z"], r["i"], self.max_points) for x, y, r in zip(xs, ys, raws)])
         img = torch.stack([self._image_chw(r["image_u8"]) for r in raws])
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
@@ -397,13 +536,11 @@ class PandaSetDataset(Dataset):
         s = stream()
         _augment_launches(aug, params, x, y, z, w, off, keys, B, n, sample_seed, s)
         GH, GW = int(self.grid_size[0]), int(self.grid_size[1])
-        x0, x1, y0, y1 = self.pc_range
         seg = torch.empty(B, GH, GW, dtype=torch.int64, device="cuda")
-        nbytes = lib.kd_bev_rasterize_ws_bytes(B, GH, GW)
+        nbytes = self._raster_ws_bytes(B, GH, GW)
         ws = workspace(nbytes, seg.device)
         lab, remap = self._labels(cls, n, s)
-        lib.call("kd_bev_rasterize", P(x), P(y), P(lab), P(off), B, n, remap, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
-                 _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws), nbytes, P(seg), s)
+        self._rasterize(x, y, lab, remap, off, B, n, GH, GW, ws, nbytes, seg, s)
         pts = torch.stack([prepare_points(*(v[a:b] for v in (x, y, z, w)), self.max_points)
                            for a, b in zip(bounds[:-1].tolist(), bounds[1:].tolist())])
         img = torch.stack([self._image_chw(r["image_u8"]) for r in raws])
@@ -433,7 +570,6 @@ class PandaSetDataset(Dataset):
             lens, (H, W, _) = staging.fill(raws, frame_keys, col_align=4, params=frame_params(augment, sample_seed, frame_keys))
         n, ns = sum(lens), staging.stride
         GH, GW = int(self.grid_size[0]), int(self.grid_size[1])
-        x0, x1, y0, y1 = self.pc_range
         ws_holder = [None] if ws_holder is None else ws_holder
         with torch.cuda.stream(side):
             cols = torch.empty(max(4 * ns, 1), dtype=torch.float32, device="cuda")
@@ -457,15 +593,14 @@ class PandaSetDataset(Dataset):
             resize = self._needs_resize((H, W))
             OW, OH = (int(self.image_size[0]), int(self.image_size[1])) if resize else (W, H)
             img = torch.empty(B, 3, OH, OW, dtype=torch.float32, device="cuda")
-            nbytes = lib.kd_bev_rasterize_ws_bytes(B, GH, GW)
+            nbytes = self._raster_ws_bytes(B, GH, GW)
             if ws_holder[0] is None or ws_holder[0].numel() < nbytes:      # this stream's own claim table: ops.workspace()
                 ws_holder[0] = torch.empty(nbytes, dtype=torch.uint8, device="cuda")   # is the compute stream's
             s = side.cuda_stream
             if augment is not None:
                 _augment_launches(augment, params, x, y, z, w, off, keys, B, n, sample_seed, s)
             lab, remap = self._labels(cls, n, s)
-            lib.call("kd_bev_rasterize", P(x), P(y), P(lab), P(off), B, n, remap, _DRIVABLE_BITS, GH, GW, _f32(x0), _f32(x1 - x0),
-                     _f32(x1), _f32(y0), _f32(y1 - y0), _f32(y1), P(ws_holder[0]), nbytes, P(seg), s)
+            self._rasterize(x, y, lab, remap, off, B, n, GH, GW, ws_holder[0], nbytes, seg, s)
             lib.call("kd_points_prepare_batch", P(x), P(y), P(z), P(w), P(off), P(keys), B, n, self.max_points,
                      int(sample_seed) & 0xFFFFFFFFFFFFFFFF, P(pts), s)
             if resize:
@@ -475,6 +610,36 @@ class PandaSetDataset(Dataset):
             if augment is not None:
                 _augment_image_launch(augment, params, img, s)
         return {"image": img, "points": pts, "segmentation": seg, "sample_token": [r["sample_token"] for r in raws]}
+
+    def label_counts(self, indices: Sequence[int] = None, batch_size: int = 16) -> np.ndarray:
+        """Host int64 [num_classes]: how many BEV cells of the frames `indices` (None: all) carry each class, under the dataset's
+        class map and label rule.  The labels path alone -- remap, rasterise, kd_label_histogram per batch of frames, one copy to
+        the host at the end -- and never augmented: what class_weights_from_counts (kdrt/losses.py) weighs the classes by."""
+        indices = list(range(len(self))) if indices is None else [int(i) for i in indices]
+        if batch_size < 1:
+            raise ValueError(f"label_counts: batch_size must be at least 1, got {batch_size}")
+        if not torch.cuda.is_available():
+            raise KDError("input preparation runs on the MI355X; there is no CPU fallback")
+        NC = self._vote_classes()
+        counts = torch.zeros(NC + 1, dtype=torch.int64, device="cuda")
+        GH, GW = int(self.grid_size[0]), int(self.grid_size[1])
+        s = stream()
+        for k in range(0, len(indices), batch_size):
+            raws = [self.load_raw(i) for i in indices[k:k + batch_size]]
+            B = len(raws)
+            lens = [int(np.shape(r["x"])[0]) for r in raws]
+            if any(int(np.shape(r[c])[0]) != m for r, m in zip(raws, lens) for c in ("y", "class")):
+                raise KDError("x, y and class must have the same length per frame")
+            n = sum(lens)
+            x, y = (torch.cat([_dev(r[c], torch.float32).reshape(-1) for r in raws]) for c in "xy")
+            cls = torch.cat([_dev(r["class"], torch.int64).reshape(-1) for r in raws])
+            off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).cuda()
+            seg = torch.empty(B, GH, GW, dtype=torch.int64, device="cuda")
+            nbytes = self._raster_ws_bytes(B, GH, GW)
+            lab, remap = self._labels(cls, n, s)
+            self._rasterize(x, y, lab, remap, off, B, n, GH, GW, workspace(nbytes, seg.device), nbytes, seg, s)
+            lib.call("kd_label_histogram", P(seg), seg.numel(), NC, P(counts), s)
+        return counts[:NC].cpu().numpy()
 
     def __getitem__(self, idx: int) -> Dict[str, torch.Tensor]:
         b = self.prepare_batch([self.load_raw(idx)])
@@ -720,11 +885,13 @@ class SyntheticRawPandaSet(PandaSetDataset):
 
     def __init__(self, n_frames: int = 64, sweep_points=169000, image_size: Tuple[int, int] = (256, 256),
                  grid_size: Tuple[int, int] = (64, 64), max_points: int = 5000, seed: int = 0, nan_frames: Sequence[int] = (),
-                 unique: int = None, source_size: Tuple[int, int] = None, device_resize: bool = False, class_map=None):
+                 unique: int = None, source_size: Tuple[int, int] = None, device_resize: bool = False,
+                 label_rule: LabelRule = None, class_map=None):
         self.root, self.scene_ids = None, []
         self.image_size, self.grid_size, self.max_points = image_size, grid_size, max_points
         self.source_size, self.device_resize = source_size, bool(device_resize)
         self.set_class_map(class_map)
+        self.set_label_rule(label_rule)
         self.pc_range = (-50, 50, -50, 50)
         self.seed, self.nan_frames = seed, set(int(i) for i in nan_frames)
         self.sweeps = [int(sweep_points)] if np.isscalar(sweep_points) else [int(v) for v in sweep_points]
@@ -757,7 +924,7 @@ class SyntheticRawPandaSet(PandaSetDataset):
 
 def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: List[str], batch_size: int = 4,
                                 num_workers: int = 0, verbose: bool = True, to_cpu: bool = None, prefetch: int = None,
-                                device_resize: bool = None, augment=None, class_map=None):
+                                device_resize: bool = None, augment=None, label_rule: LabelRule = None, class_map=None):
     """Reference signature (pandaset_dataset.py:144-160) plus `to_cpu`: batches stay on the GPU by default (the trainers'
     `.to(device)` is then free); to_cpu=True (or KD_LOADER_TO_CPU=1) returns host tensors for the reference's analysis
     scripts, which call `.numpy()` on them (test_dataset_distribution.py:22, verify_2class_distribution.py).
@@ -768,7 +935,9 @@ def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: 
     augmentation on the device, see DeviceBatchLoader; it goes to the TRAINING loader only.  The synthetic fallback serves
     ready-made tensors and ignores the setting.  `class_map` (None: the 2-class drivable labels): raw id -> class index for
     multi-class labels, see PandaSetDataset (ValueError if malformed); the synthetic fallback then draws labels in the map's
-    range of classes."""
+    range of classes.  `label_rule` (None: a cell takes the class of its first labelled point): a LabelRule, majority or priority per
+    cell, for both datasets; it needs `class_map` (ValueError without one, or when it names a class outside the map's).  The synthetic
+    fallback serves ready-made masks and only validates it."""
     if to_cpu is None:
         to_cpu = os.environ.get("KD_LOADER_TO_CPU") == "1"
     if prefetch is None:
@@ -779,12 +948,19 @@ def create_pandaset_dataloaders(root: str, train_scenes: List[str], val_scenes: 
         augment = os.environ.get("KD_LOADER_AUGMENT", "")
     augment = as_augment(augment)
     table = None if class_map is None else class_map_table(class_map)
+    if label_rule is not None:
+        if not isinstance(label_rule, LabelRule):
+            raise ValueError(f"label_rule must be a LabelRule or None, got {type(label_rule).__name__}")
+        if table is None:
+            raise ValueError("label_rule needs a class_map: with the 2-class drivable labels every rule gives the same mask")
+        label_rule.ranks(max(2, int(table.max()) + 1))
     pf = {"prefetch": prefetch, "sample_seed": int(os.environ.get("KD_LOADER_SAMPLE_SEED", "0"))}
     # under torch.distributed (one process per GPU) the FRAMES are sharded over ranks, equal counts per rank for training
     rank, world = _dist_rank_world()
     if os.path.isdir(root):
-        train_ds = PandaSetDataset(root, train_scenes, verbose=verbose, device_resize=device_resize, class_map=class_map)
-        val_ds = PandaSetDataset(root, val_scenes, verbose=verbose, device_resize=device_resize, class_map=class_map)
+        rule = {} if label_rule is None else {"label_rule": label_rule}
+        train_ds = PandaSetDataset(root, train_scenes, verbose=verbose, device_resize=device_resize, class_map=class_map, **rule)
+        val_ds = PandaSetDataset(root, val_scenes, verbose=verbose, device_resize=device_resize, class_map=class_map, **rule)
         return (DeviceBatchLoader(train_ds, batch_size, shuffle=True, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world,
                                   augment=augment, **pf),
                 DeviceBatchLoader(val_ds, batch_size, shuffle=False, num_workers=num_workers, to_cpu=to_cpu, rank=rank, world=world, **pf))

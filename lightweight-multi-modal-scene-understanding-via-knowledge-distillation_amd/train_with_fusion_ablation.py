@@ -29,6 +29,13 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
                  KD_CLASS_MAP: the path of a JSON file {"raw id": class, ...} from PandaSet's raw semantic ids to class indices
                  in [0, n-1] (0 = background; ids it does not name are background); alone it sets n to the largest class + 1.
                  No map ships with the code.  More than 4 classes: the weighted CE only (KD_HARD_LOSS unset), an fp32 teacher
+  KD_LABEL_RULE / KD_LABEL_MIN_POINTS / KD_CLASS_PRIORITY / KD_CLASS_WEIGHTS   read with a KD_CLASS_MAP only; all unset: nothing changes.
+                 KD_LABEL_RULE: unset or `first`: a BEV cell takes the class of its first labelled point in sweep order.  `majority`:
+                 the class with the most points in the cell; `priority`: the class of the highest rank.  A class needs
+                 KD_LABEL_MIN_POINTS (1) points in a cell to be eligible.  KD_CLASS_PRIORITY: the ranks, a JSON list of one integer
+                 per class or a JSON object {"class": rank} (unnamed classes 0); they break the majority's ties.
+                 KD_CLASS_WEIGHTS: unset or `default`: 0.4 / 3.5 as above.  `median_freq`: median-frequency weights from the class
+                 histogram of the training scenes' BEV labels, counted once before training.  A JSON list of n numbers: as given
 Launch with `python -m torch.distributed.run --nproc-per-node N` for data-parallel training: one process per GPU,
 frames sharded over ranks in equal counts (every rank runs the same number of steps), rank 0's initial weights
 broadcast, gradients all-reduced in buckets during backward (CE and KD training alike), BatchNorm statistics per
@@ -123,10 +130,86 @@ def multiclass_from_env(env=os.environ):
     return num_classes, class_map
 
 
+def label_rule_from_env(num_classes, env=os.environ):
+    """KD_LABEL_RULE / KD_LABEL_MIN_POINTS / KD_CLASS_PRIORITY -> None (unset or `first`: a cell takes its first labelled point's
+    class) or the LabelRule they describe, checked against `num_classes` classes.  Read only with a KD_CLASS_MAP."""
+    name = env.get("KD_LABEL_RULE", "")
+    if name in ("", "first"):
+        for k in ("KD_LABEL_MIN_POINTS", "KD_CLASS_PRIORITY"):
+            if env.get(k, ""):
+                raise ValueError(f"{k} needs KD_LABEL_RULE=majority or priority")
+        return None
+    if name not in ("majority", "priority"):
+        raise ValueError(f"KD_LABEL_RULE must be unset, 'first', 'majority' or 'priority', got {name!r}")
+    mp = env.get("KD_LABEL_MIN_POINTS", "")
+    try:
+        min_points = int(mp) if mp else 1
+    except ValueError:
+        raise ValueError(f"KD_LABEL_MIN_POINTS must be an integer >= 1, got {mp!r}") from None
+    text, priority = env.get("KD_CLASS_PRIORITY", ""), None
+    if text:
+        try:
+            priority = json.loads(text)
+        except ValueError:
+            raise ValueError(f"KD_CLASS_PRIORITY must be a JSON list of ranks or a JSON object {{\"class\": rank}}, got {text!r}") from None
+        if isinstance(priority, dict):
+            try:
+                priority = {int(k): v for k, v in priority.items()}
+            except ValueError:
+                raise ValueError(f"KD_CLASS_PRIORITY: the keys must be class indices (integers), got {text!r}") from None
+        elif not isinstance(priority, list):
+            raise ValueError(f"KD_CLASS_PRIORITY must be a JSON list of ranks or a JSON object {{\"class\": rank}}, got {text!r}")
+    from src.data_loading.pandaset_dataset import LabelRule
+    rule = LabelRule(kind=name, priority=priority, min_points=min_points)        # validates (ValueError)
+    rule.ranks(num_classes)
+    return rule
+
+
+def class_weights_from_env(num_classes, env=os.environ):
+    """KD_CLASS_WEIGHTS -> None (unset or `default`: 0.4 for the background, 3.5 for every other class), the string `median_freq`
+    (the weights come from the training labels' class histogram) or the JSON list of `num_classes` numbers it holds"""
+    text = env.get("KD_CLASS_WEIGHTS", "")
+    if text in ("", "default"):
+        return None
+    if text == "median_freq":
+        return text
+    try:
+        w = json.loads(text)
+    except ValueError:
+        w = None
+    ok = isinstance(w, list) and len(w) == num_classes and all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in w)
+    if not ok or not all(v == v and 0 <= v < float("inf") for v in w):
+        raise ValueError(f"KD_CLASS_WEIGHTS must be unset, 'default', 'median_freq' or a JSON list of {num_classes} non-negative "
+                         f"numbers, got {text!r}")
+    return [float(v) for v in w]
+
+
+_MEDIAN_FREQ = {}          # the training labels are counted once, not once per fusion variant
+
+
+def _median_freq_weights(train_loader):
+    from kdrt.losses import class_weights_from_counts
+    ds = train_loader.dataset
+    if not hasattr(ds, "label_counts"):
+        raise ValueError("KD_CLASS_WEIGHTS=median_freq counts the labels of a dataset on disk; the synthetic frames have none")
+    if "w" not in _MEDIAN_FREQ:
+        counts = ds.label_counts()
+        _MEDIAN_FREQ["w"] = class_weights_from_counts(counts)
+        log(f"  Label counts per class: {counts.tolist()}")
+    return _MEDIAN_FREQ["w"]
+
+
 def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, val_scenes, device):
     log(f"\n{'='*80}\nTRAINING: {fusion_type.upper()} FUSION\n{'='*80}")
     num_classes, class_map = multiclass_from_env()           # (None, None): the 2-class task, every call below as it was
     mc = {} if class_map is None else {"class_map": class_map}
+    weights = None
+    if class_map is not None:                                 # the label knobs are read with a class map only
+        rule = label_rule_from_env(num_classes)
+        weights = class_weights_from_env(num_classes)
+        if rule is not None:
+            mc["label_rule"] = rule
+            log(f"  Label rule: {rule}")
     train_loader, val_loader = create_pandaset_dataloaders(
         root=root, train_scenes=train_scenes, val_scenes=val_scenes,
         batch_size=int(os.environ.get("KD_BATCH_SIZE", 4)), num_workers=2, verbose=False, **mc)
@@ -144,6 +227,9 @@ def train_fusion_variant(fusion_type, fusion_out_channels, root, train_scenes, v
     if num_classes is not None:
         kw.update(num_classes=num_classes, class_weights=[0.4] + [3.5] * (num_classes - 1))
         log(f"  Classes: {num_classes} (KD_NUM_CLASSES / KD_CLASS_MAP)")
+    if weights is not None:
+        kw["class_weights"] = _median_freq_weights(train_loader) if weights == "median_freq" else weights
+        log(f"  Class weights: {kw['class_weights']} (KD_CLASS_WEIGHTS)")
     kw.update(optim_options_from_env())        # KD_EMA_DECAY, KD_EMA_WARMUP, KD_NO_DECAY_NORM_BIAS, KD_LR_MULT, KD_ACCUM_STEPS: all unset = {}
     if kw["hard_loss"] is not None:
         log(f"  Hard-label loss: {kw['hard_loss']}")
