@@ -553,6 +553,29 @@ size_t kd_seg_lovasz_ws_bytes(int B, int NC, int HW);
 int kd_seg_lovasz_fwd_bwd(const float* zs, const int64_t* target, int ignore_index, float weight, float gscale,
                           const float* gscale_dev, float* vals, float* hard_inout, float* dzs, int accumulate, int32_t* order_out,
                           int B, int NC, int HW, void* ws, size_t ws_bytes, void* stream);
+/* The opt-in online-hard-example-mining (OHEM) cross-entropy (csrc/kd_loss_ohem.hip), 2 <= NC <= 16 classes on the
+ * class buckets of kd_seg_loss_fwd_bwd.  K = the pixels kd_seg_loss_fwd_bwd keeps, n = |K|, l_i = -log p_{y_i} in fp32 from the same
+ * softmax at T = 1 (>= 0, stored with the sign bit clear, so its bits order as unsigned integers):
+ *   m = min(n, max(min_kept, ceil(n / min_divisor))) in integers,   tau_m = the m-th largest l over K (an exact order statistic),
+ *   theta = min(tau_m, lambda) with lambda = fl32(-log(thresh)) formed by the caller,   S = { i in K : l_i >= theta },
+ *   vals[0] = L = sum_S w[y] l / sum_S w[y],   dzs = gscale * gscale_dev[0] * (dL/dzs + alpha*T^2 dKL/dzs) with S held constant:
+ *   w[y_i] (p_ij - [j == y_i]) / sum_S w on S, 0 on the rest of K; the KL value and gradient run over all pixels and keep the bits
+ *   of kd_seg_loss_fwd_bwd.  At least m pixels above the threshold: all of them are kept; otherwise the m hardest with every tie at
+ *   tau_m: S is a function of the values alone.  min_divisor = 1 or lambda = 0 keeps all of K (the weighted CE).  n = 0: vals[0] is NaN
+ *   like the CE, no hard-label gradient.  A NaN l sorts above every number and is kept.
+ * vals holds 8 floats: [0] L  [1] KL (per-pixel mean; 0 if zt NULL)  [2] sum_S w  [3] the weighted CE over all of K  [4] theta
+ * [5] |S| / n  [6..7] 0.  counts_out (may be NULL): int64[3] = n, m, |S|.  nll_out (may be NULL; for tests): float [B*HW], l or -1
+ * outside K.  keep_out (may be NULL; for tests): uint8 [B*HW], 1 on S.  zt NULL: no KL; dzs NULL: forward only.
+ * Selection: a radix select over the 31 value bits in digits of 11 + 10 + 10 bits, histograms privatised in LDS and flushed with
+ * integer atomics, m, the running rank and theta on the device.  Seven launches with dzs, six without; no floating-point atomics,
+ * no host reads: capturable, bit-identical from call to call.  NC outside 2..16, B < 1, HW < 1 or B * HW >= 2^31 is KD_ERR_SHAPE; a
+ * lambda that is not finite and >= 0, min_kept < 1, min_divisor < 1 or a NULL zs / target / vals is KD_ERR_ARG; ws =
+ * kd_seg_ohem_ws_bytes(B * HW) bytes, 8-byte aligned, else KD_ERR_WORKSPACE / KD_ERR_ALIGN.  A refused call writes nothing. */
+size_t kd_seg_ohem_ws_bytes(int64_t npix);
+int kd_seg_ohem_fwd_bwd(const float* zs, const float* zt, const int64_t* target, const float* class_w, int ignore_index, float T,
+                        float alpha, float gscale, const float* gscale_dev, float lambda, int64_t min_kept, int64_t min_divisor,
+                        float* vals, int64_t* counts_out, float* dzs, float* nll_out, uint8_t* keep_out, int B, int NC, int HW,
+                        void* ws, size_t ws_bytes, void* stream);
 size_t kd_mse_ws_bytes(int64_t n);
 int kd_mse_fwd_bwd(const float* a, const float* b, int64_t n, float gcoef, const float* gscale_dev, float* loss,
                    float* da, void* ws, size_t ws_bytes, void* stream);

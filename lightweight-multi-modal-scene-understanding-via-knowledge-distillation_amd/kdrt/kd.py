@@ -14,7 +14,7 @@ import torch
 from . import gradsink, ops, units
 from .ddp import BucketedAllReduce
 from .lib import KDError
-from .losses import ChannelKD, kd_objective, kd_objective_backward
+from .losses import ChannelKD, LovaszLoss, OhemCE, RegionLoss, kd_objective, kd_objective_backward
 from .optim import AccumCycle, FusedAdamW
 
 
@@ -69,6 +69,11 @@ class KDStep(metaclass=_TakesAccumSteps):
         # the CE.  Data parallel: the Tversky sums cover each rank's own shard, the reducer averages the per-rank gradients.
         # A kdrt.losses.LovaszLoss adds weight * Lovasz-Softmax to its base term (the CE or a RegionLoss): a mean over images, so
         # with equal shards the averaged per-rank gradient is the global batch's.
+        # A kdrt.losses.OhemCE averages the weighted CE over the mined pixels only (2 to 16 classes): one kd_seg_ohem_fwd_bwd call in
+        # the CE call's place, no host read, so GraphedKDStep replays it unchanged.  Each rank mines its own shard.
+        if hard_loss is not None and not isinstance(hard_loss, (RegionLoss, LovaszLoss, OhemCE)):
+            raise ValueError("hard_loss must be a kdrt.losses.RegionLoss, a kdrt.losses.LovaszLoss, a kdrt.losses.OhemCE or None, "
+                             f"got {type(hard_loss).__name__}")
         self.hard_loss = hard_loss
         self.reducer = reducer
         self.sink = gradsink.install(optimizer.flat, reducer)      # backward kernels write into the flat grad buffer

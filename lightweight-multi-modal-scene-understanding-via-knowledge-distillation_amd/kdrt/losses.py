@@ -7,6 +7,8 @@
                   form (csrc/kd_loss_region.hip; definition in DESIGN.md section 3)
   lovasz_seg_loss : the opt-in Lovasz-Softmax term (LovaszLoss) added to the weighted CE or to a RegionLoss: the base call, then
                   csrc/kd_loss_lovasz.hip on the same stream, adding its value and its gradient to what the base call wrote
+  ohem_seg_loss : the opt-in online-hard-example-mining cross-entropy (OhemCE) in place of the weighted CE, 2 to 16 classes: an exact
+                  order-statistic selection on the device, then the CE over the kept pixels (csrc/kd_loss_ohem.hip)
   feature_mse   : F.mse_loss forward + gradient
   channel_kd    : the opt-in channel-wise distillation feature term (ChannelKD; Shu et al., ICCV 2021) in the feature MSE's place:
                   a temperature softmax down the H*W positions of every channel of every image, KL to the teacher's
@@ -312,6 +314,93 @@ def lovasz_seg_loss(logits, target, spec: LovaszLoss, class_weights: Optional[to
     return hard, kl, parts
 
 
+@dataclass(frozen=True)
+class OhemCE:
+    """Online hard example mining for the weighted cross-entropy, 2 to 16 classes:
+
+      l_i = -log p_{y_i} over the n pixels K the weighted CE keeps,   m = min(n, max(min_kept, ceil(n / min_divisor)))
+      theta = min(m-th largest l, -log(thresh)),   S = { i in K : l_i >= theta },   L_hard = sum_S w[y] l / sum_S w[y]
+
+    Every pixel whose probability of its label is at most `thresh` is kept when there are at least m of them; otherwise the m
+    hardest, with every tie at the m-th.  S is held constant in the gradient.  thresh = 1 or min_divisor = 1 keeps all of K: the
+    weighted CE.  min_divisor = 16 is BiSeNet's n/16.  Mining is a training device: Trainer validates with the plain weighted CE.
+    Mining is per call: under data parallelism each rank mines its own shard (as the Tversky sums of RegionLoss cover one shard)
+    and the reducer averages the per-rank gradients; there is no collective."""
+    thresh: float = 0.7
+    min_divisor: int = 16
+    min_kept: int = 1
+
+    def __post_init__(self):
+        t = self.thresh
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or not 0 < t <= 1:
+            raise ValueError(f"OhemCE: thresh must be a finite number in (0, 1], got {t!r}")
+        for k in ("min_divisor", "min_kept"):
+            v = getattr(self, k)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"OhemCE: {k} must be an integer >= 1, got {v!r}")
+
+    def lam(self):
+        """lambda = fl32(-log(thresh)), the cut-off on l the kernel receives (+0 for thresh = 1)"""
+        return float(np.float32(-math.log(self.thresh))) + 0.0
+
+
+OHEM_VALS = 8             # floats kd_seg_ohem_fwd_bwd writes: L, KL, sum_S w, the CE over all of K, theta, |S| / n, 2 spare
+_I64_MAX = 2 ** 63 - 1
+
+
+def _ohem_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, vals, dzs):
+    B, NC, H, W = zs.shape
+    nbytes = lib.kd_seg_ohem_ws_bytes(B * H * W)
+    ws = ops.workspace(nbytes, zs.device)
+    lib.call("kd_seg_ohem_fwd_bwd", P(zs), P(zt), P(target), P(class_w), int(ignore_index), float(T), float(alpha), 1.0, P(gdev),
+             spec.lam(), min(spec.min_kept, _I64_MAX), min(spec.min_divisor, _I64_MAX), P(vals), None, P(dzs), None, None,
+             B, NC, H * W, P(ws), nbytes, stream())
+
+
+class _OhemLossFn(torch.autograd.Function):
+    """_SegLossFn with the mined CE as the hard-label term: forward values only, backward one more fused call."""
+
+    @staticmethod
+    def forward(ctx, zs, zt, target, class_w, ignore_index, T, alpha, spec):
+        ops.require_gpu_tensor(zs, "ohem_seg_loss")
+        if not isinstance(spec, OhemCE):
+            raise KDError(f"ohem_seg_loss: spec must be a kdrt.losses.OhemCE, got {type(spec).__name__}")
+        zs_c = zs.detach().contiguous()
+        zt_c = None if zt is None else zt.detach().contiguous()
+        target = target.contiguous()
+        if target.dtype != torch.int64:
+            raise KDError("segmentation target must be int64")
+        _check_target(zs_c, target)
+        _check_class_weights(zs_c, class_w)
+        vals = torch.empty(OHEM_VALS, device=zs.device, dtype=torch.float32)
+        _ohem_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, vals, None)
+        ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec)
+        kl, ce_all, theta, kept = vals[1], vals[3], vals[4], vals[5]
+        ctx.mark_non_differentiable(kl, ce_all, theta, kept)
+        return vals[0], kl, ce_all, theta, kept
+
+    @staticmethod
+    def backward(ctx, g_hard, *_):
+        # the gradient through `hard` is d(L_hard + alpha*T^2*KL)/dzs (kd_objective adds KL's value separately)
+        zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec = ctx.args
+        vals = torch.empty(OHEM_VALS, device=zs_c.device, dtype=torch.float32)
+        dzs = torch.empty_like(zs_c)
+        _ohem_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, g_hard.contiguous().view(1), vals, dzs)
+        return dzs, None, None, None, None, None, None, None
+
+
+def ohem_seg_loss(logits, target, spec: OhemCE, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
+                  teacher_logits: Optional[torch.Tensor] = None, T: float = 4.0, alpha: float = 1.0):
+    """-> (hard, kl, parts): seg_loss with the weighted CE averaged over the mined pixels only (see OhemCE), 2 to 16 classes.  The
+    gradient that flows back through `hard` is that of hard + alpha*T^2*kl, the kept set held constant.
+    parts = {"ce_all", "theta", "kept"}: the weighted CE over every kept-label pixel (for logging), the cut-off on -log p_y and the
+    kept share |S| / n, device scalars, detached.  Data parallel: each rank mines its own shard."""
+    if teacher_logits is None:
+        alpha = 0.0
+    hard, kl, ce_all, theta, kept = _OhemLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T, alpha, spec)
+    return hard, kl, {"ce_all": ce_all, "theta": theta, "kept": kept}
+
+
 class _MSEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -431,6 +520,8 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
     and "tversky".  Under data parallelism the Tversky sums cover this rank's shard (see RegionLoss).
     hard_loss (a LovaszLoss): weight * Lovasz is added to its base term (the CE or a RegionLoss); parts["ce"] carries the sum and
     parts gains "lovasz" and "class_lovasz" (and the base's "focal" / "tversky").  A mean over images: exact under data parallelism.
+    hard_loss (an OhemCE): the weighted CE over the mined pixels takes the CE's place (2 to 16 classes); parts["ce"] carries it and
+    parts gains "ce_all" (the CE over every labelled pixel), "ohem_theta" and "ohem_kept".  Each rank mines its own shard.
     feature_loss (a ChannelKD): beta * (CWD(camera_feat) + CWD(lidar_feat)) at its tau takes the two MSEs' place and parts carries
     "cwd_cam" / "cwd_lidar" instead of "mse_cam" / "mse_lidar".  A mean over images as well.  beta needs re-tuning (see ChannelKD)."""
     extra = {}
@@ -438,6 +529,9 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
         _check_feature_spec(feature_loss)
     if hard_loss is None:
         ce, kl = seg_loss(student_logits, target, class_weights, ignore_index, teacher_logits, T, alpha)
+    elif isinstance(hard_loss, OhemCE):
+        ce, kl, op = ohem_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
+        extra = {"ce_all": op["ce_all"], "ohem_theta": op["theta"], "ohem_kept": op["kept"]}
     elif isinstance(hard_loss, LovaszLoss):
         ce, kl, extra = lovasz_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
     else:
@@ -463,6 +557,8 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     hard_loss as in kd_objective: the region-loss call writes dL/dlogits together with L_hard / KL in the CE call's place; the
     Lovasz call follows its base call on the same stream and adds its value and its gradient to what that call wrote, before the
     final kernel reads the hard-label term (parts gains "lovasz"; "class_lovasz" comes from the autograd form only).
+    An OhemCE makes ONE kd_seg_ohem_fwd_bwd call in the CE call's place (value, KL and dL/dlogits; parts gains "ce_all",
+    "ohem_theta", "ohem_kept").
     feature_loss (a ChannelKD): each map gets ONE kd_feat_cwd_fwd_bwd call that writes the value and the gradient, with
     gcoef = fl32(fl32(tau / (B*C)) * fl32(beta)) -- the product the autograd form's backward call forms on the device from its
     gcoef fl32(tau / (B*C)) and the upstream gradient fl32(beta), so both forms store the same gradient bits; the gradient is
@@ -494,6 +590,10 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     if hard_loss is None:
         lib.call("kd_seg_loss_fwd_bwd", P(zs_c), P(zt_c), P(target), P(class_weights), int(ignore_index), float(T), float(alpha),
                  1.0, None, P(vals), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
+    elif isinstance(hard_loss, OhemCE):
+        hard = torch.empty(OHEM_VALS, device=dev, dtype=torch.float32)
+        _ohem_call(hard_loss, zs_c, zt_c, target, class_weights, ignore_index, T, alpha, None, hard, dzs)
+        extra = {"ce_all": hard[3], "ohem_theta": hard[4], "ohem_kept": hard[5]}
     elif isinstance(hard_loss, LovaszLoss):
         hard = torch.zeros(REGION_VALS, device=dev, dtype=torch.float32)
         lov = torch.empty(LOVASZ_VALS, device=dev, dtype=torch.float32)

@@ -23,7 +23,7 @@ from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
 from kdrt.lib import KDError
-from kdrt.losses import ChannelKD, LovaszLoss, RegionLoss, confusion, lovasz_seg_loss, region_seg_loss, seg_loss
+from kdrt.losses import ChannelKD, LovaszLoss, OhemCE, RegionLoss, confusion, lovasz_seg_loss, ohem_seg_loss, region_seg_loss, seg_loss
 from kdrt.optim import AccumCycle, FusedAdamW, check_accum_steps, decay_groups
 
 try:
@@ -141,11 +141,18 @@ class Trainer(metaclass=_TakesNumClasses):
         # weights then enter the focal term only).  Data parallel: the Tversky sums cover each rank's own shard of the batch.
         # hard_loss (kdrt.losses.LovaszLoss): its base term (the weighted CE or a RegionLoss) + weight * Lovasz-Softmax, a mean over
         # images (exact under data parallelism with equal shards); maps of at most 128 x 128 pixels.
-        if hard_loss is not None and not isinstance(hard_loss, (RegionLoss, LovaszLoss)):
-            raise ValueError(f"hard_loss must be a kdrt.losses.RegionLoss, a kdrt.losses.LovaszLoss or None, got {type(hard_loss).__name__}")
+        # hard_loss (kdrt.losses.OhemCE): the weighted CE over the mined pixels, 2 to 16 classes.  Mining is a training device:
+        # validation reports the plain weighted CE.  Data parallel: each rank mines its own shard.
+        if hard_loss is not None and not isinstance(hard_loss, (RegionLoss, LovaszLoss, OhemCE)):
+            raise ValueError("hard_loss must be a kdrt.losses.RegionLoss, a kdrt.losses.LovaszLoss, a kdrt.losses.OhemCE or None, "
+                             f"got {type(hard_loss).__name__}")
         self.hard_loss = hard_loss
+        self.val_criterion = None                              # None: validate with the training criterion
         if hard_loss is None:
             self.criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
+        elif isinstance(hard_loss, OhemCE):
+            self.criterion = lambda logits, seg: ohem_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
+            self.val_criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
         elif isinstance(hard_loss, LovaszLoss):
             self.criterion = lambda logits, seg: lovasz_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
         else:
@@ -207,11 +214,11 @@ class Trainer(metaclass=_TakesNumClasses):
         """num_classes (None, the default: the reference's 2-class metrics on whatever the head emits): the width of the confusion
         matrix of training and validation, 2 to 16; it must agree with the length of class_weights.  The head's own class count
         is the model's (CompleteSegmentationModel(num_classes=...)); more than 4 classes need the same-resolution head, the weighted
-        CE (hard_loss=None) and, for KD, an fp32 teacher."""
+        CE (hard_loss=None) or its mined form (an OhemCE) and, for KD, an fp32 teacher."""
         if num_classes is not None:
             if self.class_weights is not None and self.class_weights.numel() != num_classes:
                 raise ValueError(f"class_weights has {self.class_weights.numel()} entries for num_classes={num_classes}")
-            if self.hard_loss is not None and num_classes > 4:
+            if self.hard_loss is not None and not isinstance(self.hard_loss, OhemCE) and num_classes > 4:
                 raise KDError(f"hard_loss (RegionLoss / LovaszLoss) holds at most 4 classes, num_classes={num_classes}")
         self.num_classes = num_classes
         self.metric_classes = 2 if num_classes is None else num_classes
@@ -301,7 +308,7 @@ class Trainer(metaclass=_TakesNumClasses):
                 pts = batch["points"].to(self.device, non_blocking=True)
                 seg = batch["segmentation"].to(self.device, non_blocking=True)
                 logits = self.model(imgs, pts)
-                total += self.criterion(logits, seg)
+                total += (self.val_criterion or self.criterion)(logits, seg)
                 metrics.update(logits, seg)
         out = metrics.compute()
         self.val_confusion = metrics.confusion.copy()

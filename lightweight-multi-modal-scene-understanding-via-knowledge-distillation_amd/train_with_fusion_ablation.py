@@ -13,6 +13,9 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
                  `ce_lovasz`: the weighted cross-entropy + KD_LOVASZ_WEIGHT (1.0) * Lovasz-Softmax (kdrt.losses.LovaszLoss: the
                  direct surrogate of the Jaccard index, per image over the classes present; label maps of at most 128 x 128).
                  `focal_tversky_lovasz`: the same term on top of the RegionLoss the three knobs above describe
+                 `ohem`: the weighted cross-entropy averaged over the mined pixels only (kdrt.losses.OhemCE, 2 to 16 classes): every
+                 pixel whose probability of its label is at most KD_OHEM_THRESH (0.7), and at least max(KD_OHEM_MIN_KEPT (1),
+                 n / KD_OHEM_MIN_DIVISOR (16)) of the n labelled pixels; validation reports the plain weighted CE
   KD_FEATURE_LOSS   with KD_TEACHER: unset or `mse`: the feature MSE between the student's and the teacher's camera_feat / lidar_feat
                  maps.  `cwd`: channel-wise distillation in its place (kdrt.losses.ChannelKD: a temperature softmax over the
                  positions of every channel, KL to the teacher's) at temperature KD_CWD_TAU (4.0); beta keeps its meaning but
@@ -28,7 +31,7 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
                  the metrics are n wide and the class weights are 0.4 for the background and 3.5 for every other class.
                  KD_CLASS_MAP: the path of a JSON file {"raw id": class, ...} from PandaSet's raw semantic ids to class indices
                  in [0, n-1] (0 = background; ids it does not name are background); alone it sets n to the largest class + 1.
-                 No map ships with the code.  More than 4 classes: the weighted CE only (KD_HARD_LOSS unset), an fp32 teacher
+                 No map ships with the code.  More than 4 classes: the weighted CE (KD_HARD_LOSS unset) or `ohem`, an fp32 teacher
   KD_LABEL_RULE / KD_LABEL_MIN_POINTS / KD_CLASS_PRIORITY / KD_CLASS_WEIGHTS   read with a KD_CLASS_MAP only; all unset: nothing changes.
                  KD_LABEL_RULE: unset or `first`: a BEV cell takes the class of its first labelled point in sweep order.  `majority`:
                  the class with the most points in the cell; `priority`: the class of the highest rank.  A class needs
@@ -74,14 +77,18 @@ def build_model(fusion_type, fusion_out_channels, device, num_classes=2, base_ch
 
 
 def hard_loss_from_env(env=os.environ):
-    """KD_HARD_LOSS -> None (weighted CE), the RegionLoss the KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA knobs describe, or a
-    LovaszLoss of weight KD_LOVASZ_WEIGHT over either (`ce_lovasz`, `focal_tversky_lovasz`)"""
+    """KD_HARD_LOSS -> None (weighted CE), the RegionLoss the KD_FOCAL_GAMMA / KD_TVERSKY_ALPHA / KD_TVERSKY_BETA knobs describe, a
+    LovaszLoss of weight KD_LOVASZ_WEIGHT over either (`ce_lovasz`, `focal_tversky_lovasz`), or the OhemCE of KD_OHEM_THRESH /
+    KD_OHEM_MIN_DIVISOR / KD_OHEM_MIN_KEPT (`ohem`); a value OhemCE refuses is a ValueError"""
     name = env.get("KD_HARD_LOSS", "")
     if name in ("", "ce"):
         return None
-    if name not in ("focal_tversky", "ce_lovasz", "focal_tversky_lovasz"):
-        raise ValueError(f"KD_HARD_LOSS must be unset, 'ce', 'focal_tversky', 'ce_lovasz' or 'focal_tversky_lovasz', got {name!r}")
-    from kdrt.losses import LovaszLoss, RegionLoss
+    if name not in ("focal_tversky", "ce_lovasz", "focal_tversky_lovasz", "ohem"):
+        raise ValueError(f"KD_HARD_LOSS must be unset, 'ce', 'focal_tversky', 'ce_lovasz', 'focal_tversky_lovasz' or 'ohem', got {name!r}")
+    from kdrt.losses import LovaszLoss, OhemCE, RegionLoss
+    if name == "ohem":                     # float() / int() of an unparsable value and OhemCE's own validation raise ValueError
+        return OhemCE(thresh=float(env.get("KD_OHEM_THRESH", 0.7)), min_divisor=int(env.get("KD_OHEM_MIN_DIVISOR", 16)),
+                      min_kept=int(env.get("KD_OHEM_MIN_KEPT", 1)))
     region = None
     if name != "ce_lovasz":
         region = RegionLoss(gamma=float(env.get("KD_FOCAL_GAMMA", 2.0)), a=float(env.get("KD_TVERSKY_ALPHA", 0.7)),
