@@ -606,6 +606,28 @@ int kd_kd_objective_final(const float* ce_kl, const float* slab_c, int64_t n_c, 
 size_t kd_feat_cwd_ws_bytes(int B, int HW, int C);
 int kd_feat_cwd_fwd_bwd(const float* s, const float* t, int B, int HW, int C, float tau, float gcoef, const float* gscale_dev,
                         float* val, float* ds, float* stats_out, void* ws, size_t ws_bytes, void* stream);
+/* The opt-in pair-wise distillation feature term in Gram form (csrc/kd_loss_pair.hip; Liu et al., CVPR 2019) of two
+ * NHWC feature matrices s [B*HW, Cs] and t [B*HW, Ct] (row-major, what ops.nhwc_view yields), n = HW positions per image:
+ *   r_i = sqrt(sum_c x_ic^2), xh_i = x_i / r_i if r_i > 1e-12 else 0 (such a row also receives no gradient),  a_ij = xh_i . xh_j,
+ *   L_b = 1/n^2 sum_ij (a^S_ij - a^T_ij)^2 = 1/n^2 (|Gss|_F^2 - 2 |Gts|_F^2 + |Gtt|_F^2),  Gss = Sh^T Sh, Gts = Th^T Sh, Gtt = Th^T Th,
+ *   val[0] = PAIR = 1/B sum_b L_b                       (not scaled by gcoef),
+ *   ds     = k * (gh_i - xh_i (xh_i . gh_i)) / r_i,  gh = Sh Gss - Th Gts,  k = gcoef * (gscale_dev ? gscale_dev[0] : 1) formed once in
+ *   fp32 (ds NULL: forward only); the caller passes gcoef = 4 / (B n^2) times whatever it folds in.
+ * img_vals_out (may be NULL; for tests): the B per-image values L_b.  The n x n affinities are never formed: O(n C^2) work on the exact
+ * fp32 MFMA (a k-ordered fp32 fma chain), sqrtf and a true division for the norms.  kd_feat_pair_slices(B, HW): the row slices an image
+ * is cut into for the Gram pass (1 once B fills the device; a function of B and HW alone; 0 for an unsupported B or HW).  Launches: Gram
+ * partials per (image, slice) to a slab; the slice join with sum gss^2 - 2 gts^2 + gtt^2 in double; the per-image values and their
+ * mean in double in one block; with ds the gradient pass ([Gss; Gts] resident in LDS when (Csp + Ctp) * Csp * 4 <= 128 KiB, widths
+ * padded to 32; streamed otherwise).  No atomics, no host reads: capturable, bit-identical from call to call.  s and t go through
+ * the same instruction sequence: identical bits in both (s == t as pointers is allowed) give val[0] == 0 and ds == +-0 exactly.
+ * The value and the gradient are differences of quantities of order 1 (the cancellation note).
+ * A width that is no multiple of 4 or outside 4..256, HW < 1, HW > 2^30 or B < 1 is KD_ERR_SHAPE; a NULL s / t / val / ws or a gcoef that is not
+ * finite is KD_ERR_ARG; s, t, ds or ws not 16-byte aligned is KD_ERR_ALIGN; ws = kd_feat_pair_ws_bytes(B, HW, Cs, Ct) bytes (0 for an
+ * unsupported shape), else KD_ERR_WORKSPACE.  A refused call launches and writes nothing. */
+size_t kd_feat_pair_ws_bytes(int B, int HW, int Cs, int Ct);
+int kd_feat_pair_slices(int B, int HW);
+int kd_feat_pair_fwd_bwd(const float* s, const float* t, int B, int HW, int Cs, int Ct, float gcoef, const float* gscale_dev,
+                         float* val, float* ds, float* img_vals_out, void* ws, size_t ws_bytes, void* stream);
 /* pred[B*HW] = argmax over the NC (1..4) classes, first maximum wins; conf[M*M] (ACCUMULATED into) counts a pixel at [t, argmax]
  * when t != ignore_index and 0 <= t < M and argmax < M: M (1..4) is the width of the matrix, independent of NC.  Either of conf
  * and pred may be NULL; target NULL: no counting. */

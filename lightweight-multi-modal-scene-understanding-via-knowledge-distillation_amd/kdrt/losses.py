@@ -13,6 +13,9 @@
   channel_kd    : the opt-in channel-wise distillation feature term (ChannelKD; Shu et al., ICCV 2021) in the feature MSE's place:
                   a temperature softmax down the H*W positions of every channel of every image, KL to the teacher's
                   (csrc/kd_loss_cwd.hip; definition in DESIGN.md section 3)
+  pair_kd       : the opt-in pair-wise distillation feature term (PairKD; Liu et al., CVPR 2019) in the feature MSE's place: the cosine
+                  similarities of all pairs of positions of a map against the teacher's, formed from C x C Gram matrices, never the
+                  n x n affinities (csrc/kd_loss_pair.hip; definition in DESIGN.md section 3)
   kd_objective  : CE + alpha*T^2*KL + beta*(MSE(cam) + MSE(lidar))   (the
                   reference has no KD code -- this definition is the build's specification)
   kd_objective_backward : the same objective AND its backward pass for the training step: every loss kernel
@@ -454,9 +457,37 @@ class ChannelKD:
 CWD_MAX_C = 512           # csrc/kd_loss_cwd.hip: a thread owns 4 channels, a workgroup of 256 threads at least 2 rows
 
 
+@dataclass(frozen=True)
+class PairKD:
+    """Pair-wise distillation (Liu et al., "Structured Knowledge Distillation for Semantic Segmentation", CVPR 2019; DESIGN.md
+    section 3) as the feature term of the KD objective, in the feature MSE's place.  S [B, n, Cs] and T [B, n, Ct] are the NHWC
+    matrices of the student's and the teacher's map, n = H*W; for image b:
+
+      r_i   = sqrt(sum_c x_ic^2)                 for the rows of S_b and of T_b
+      xh_i  = x_i / r_i  if r_i > 1e-12, else 0  (such a row also receives no gradient: empty BEV cells are all-zero after ReLU)
+      a_ij  = xh_i . xh_j                        the cosine similarity of positions i and j
+      L_b   = 1/n^2 * sum_ij (a^S_ij - a^T_ij)^2 = 1/n^2 * (|Gss|_F^2 - 2 |Gts|_F^2 + |Gtt|_F^2)
+              Gss = Sh^T Sh [Cs x Cs],  Gts = Th^T Sh [Ct x Cs],  Gtt = Th^T Th [Ct x Ct]
+      PAIR  = 1/B * sum_b L_b
+      dPAIR/dSh_b = 4/(B n^2) * (Sh_b Gss - Th_b Gts) =: gh,     dPAIR/dS_i = (gh_i - xh_i (xh_i . gh_i)) / r_i
+
+    It matches WHICH positions look alike, not the features themselves: no adapter, no parameter, no pooling (the Gram form costs
+    O(n C^2), so the full-resolution map is affordable), and the two widths need not be equal (multiples of 4 from 4 to 256).
+    beta keeps its meaning, but the term's magnitude is not the MSE's: with the 1/n^2 mean the gradient entries at n = 4096 are of
+    order 1e-7 before beta -- re-tune beta when switching.
+    The term is a mean over images: with equal shards under data parallelism the mean of the per-rank values IS the value of the
+    global batch and the reducer's averaged gradient its gradient.
+    The Gram form subtracts quantities of order 1: once the student's map is within about 1 % of the teacher's, the relative error
+    of the small gradient that is left grows (absolute in the scale of the cancelling terms)."""
+
+
+PAIR_MIN_C, PAIR_MAX_C = 4, 256   # csrc/kd_loss_pair.hip: widths in multiples of 4
+
+
 def _check_feature_spec(spec):
-    if not isinstance(spec, ChannelKD):
-        raise KDError(f"the feature loss must be a kdrt.losses.ChannelKD (or None for the feature MSE), got {type(spec).__name__}")
+    if not isinstance(spec, (ChannelKD, PairKD)):
+        raise KDError("the feature loss must be a kdrt.losses.ChannelKD or kdrt.losses.PairKD (or None for the feature MSE), got "
+                      f"{type(spec).__name__}")
 
 
 def _check_cwd_pair(a, b):
@@ -512,6 +543,68 @@ def channel_kd(student_feat, teacher_feat, tau: float = 4.0):
     return _ChannelKDFn.apply(student_feat, teacher_feat, float(tau))
 
 
+def _check_pair_pair(a, b):
+    """the kernel indexes the maps as [B*H*W, Cs] and [B*H*W, Ct]: one B, H, W, either width"""
+    if not torch.is_tensor(a) or not torch.is_tensor(b) or a.dim() != 4 or b.dim() != 4:
+        raise KDError("pair_kd: two [B, C, H, W] tensors expected")
+    ops.require_gpu_tensor(a, "pair_kd")
+    if a.device != b.device or a.shape[0] != b.shape[0] or tuple(a.shape[2:]) != tuple(b.shape[2:]):
+        raise KDError(f"pair_kd: student map {tuple(a.shape)} on {a.device} and teacher map {tuple(b.shape)} on {b.device} must share "
+                      "B, H, W and the device")
+    for C in (a.shape[1], b.shape[1]):
+        if C % 4 != 0 or C < PAIR_MIN_C or C > PAIR_MAX_C:
+            raise KDError(f"pair_kd: {C} channels unsupported (a multiple of 4 from {PAIR_MIN_C} to {PAIR_MAX_C})")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise KDError(f"pair_kd: fp32 maps expected, got {a.dtype} and {b.dtype}")
+
+
+def _pair_call(am, bm, geom, gcoef, gdev, val, ds):
+    """one kd_feat_pair_fwd_bwd call on the NHWC matrices am [B*H*W, Cs], bm [B*H*W, Ct]: val[0] = PAIR, ds = gcoef * gdev[0] * (B n^2 / 4)
+    * dPAIR/dS"""
+    B, H, W = geom
+    Cs, Ct = am.shape[1], bm.shape[1]
+    nbytes = lib.kd_feat_pair_ws_bytes(B, H * W, Cs, Ct)
+    ws = ops.workspace(nbytes, am.device)
+    lib.call("kd_feat_pair_fwd_bwd", P(am), P(bm), B, H * W, Cs, Ct, float(gcoef), P(gdev), P(val), P(ds), None, P(ws), nbytes, stream())
+
+
+def _pair_gcoef(geom):
+    """4 / (B n^2), the host's double rounded to fp32 by the call"""
+    B, H, W = geom
+    return 4.0 / (float(B) * float(H * W) * float(H * W))
+
+
+class _PairKDFn(torch.autograd.Function):
+    """_ChannelKDFn's shape: forward the value only; backward one more call with the upstream gradient read from device memory, so the
+    gradient coefficient is k = fl32(fl32(4 / (B n^2)) * g) -- with g = fl32(beta) from the objective's autograd graph the product
+    kd_objective_backward folds into gcoef on the host."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        _check_pair_pair(a, b)
+        am, geom = ops.nhwc_view(a.detach())
+        bm, _ = ops.nhwc_view(b.detach())
+        val = torch.empty(1, device=a.device, dtype=torch.float32)
+        _pair_call(am, bm, geom, 0.0, None, val, None)
+        ctx.am, ctx.bm, ctx.geom = am, bm, geom
+        return val[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        am, bm, geom = ctx.am, ctx.bm, ctx.geom
+        ds = torch.empty_like(am)
+        val = torch.empty(1, device=am.device, dtype=torch.float32)
+        _pair_call(am, bm, geom, _pair_gcoef(geom), g.contiguous().view(1), val, ds)
+        return ops.nchw_from_matrix(ds, geom), None
+
+
+def pair_kd(student_feat, teacher_feat):
+    """PAIR(student_feat, teacher_feat) of two fp32 maps [B, Cs, H, W] and [B, Ct, H, W] (see PairKD): a device scalar whose gradient
+    flows to the student map only.  KDError on CPU tensors, a dtype other than fp32, differing B, H, W or devices, and on a width that is
+    no multiple of 4 or outside 4..256."""
+    return _PairKDFn.apply(student_feat, teacher_feat)
+
+
 def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
                  class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
                  feature_loss=None, hard_loss=None):
@@ -523,7 +616,9 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
     hard_loss (an OhemCE): the weighted CE over the mined pixels takes the CE's place (2 to 16 classes); parts["ce"] carries it and
     parts gains "ce_all" (the CE over every labelled pixel), "ohem_theta" and "ohem_kept".  Each rank mines its own shard.
     feature_loss (a ChannelKD): beta * (CWD(camera_feat) + CWD(lidar_feat)) at its tau takes the two MSEs' place and parts carries
-    "cwd_cam" / "cwd_lidar" instead of "mse_cam" / "mse_lidar".  A mean over images as well.  beta needs re-tuning (see ChannelKD)."""
+    "cwd_cam" / "cwd_lidar" instead of "mse_cam" / "mse_lidar".  A mean over images as well.  beta needs re-tuning (see ChannelKD).
+    feature_loss (a PairKD): beta * (PAIR(camera_feat) + PAIR(lidar_feat)) takes the two MSEs' place and parts carries "pair_cam" /
+    "pair_lidar".  A mean over images as well.  beta needs re-tuning (see PairKD)."""
     extra = {}
     if feature_loss is not None:
         _check_feature_spec(feature_loss)
@@ -541,6 +636,10 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
         names = ("mse_cam", "mse_lidar")
         mse_c = feature_mse(student_mids["camera_feat"], teacher_mids["camera_feat"])
         mse_l = feature_mse(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
+    elif isinstance(feature_loss, PairKD):
+        names = ("pair_cam", "pair_lidar")
+        mse_c = pair_kd(student_mids["camera_feat"], teacher_mids["camera_feat"])
+        mse_l = pair_kd(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
     else:
         names = ("cwd_cam", "cwd_lidar")
         mse_c = channel_kd(student_mids["camera_feat"], teacher_mids["camera_feat"], feature_loss.tau)
@@ -563,6 +662,8 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     gcoef = fl32(fl32(tau / (B*C)) * fl32(beta)) -- the product the autograd form's backward call forms on the device from its
     gcoef fl32(tau / (B*C)) and the upstream gradient fl32(beta), so both forms store the same gradient bits; the gradient is
     deposited exactly as the MSE's is, and kd_kd_total forms the total from the two values ("cwd_cam" / "cwd_lidar").
+    feature_loss (a PairKD): the same with ONE kd_feat_pair_fwd_bwd call per map and gcoef = fl32(fl32(4 / (B n^2)) * fl32(beta))
+    ("pair_cam" / "pair_lidar").
 
     Same values and the same gradient bits as the autograd formulation, fewer passes: the segmentation-loss call writes
     dL/dlogits together with CE / KL; each feature MSE writes its gradient in the pass that sums its value, and that
@@ -610,16 +711,25 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     gradsink.drop_pending()
     if feature_loss is not None:
         _check_feature_spec(feature_loss)
-        tau = float(feature_loss.tau)
+        pair = isinstance(feature_loss, PairKD)
+        names = ("pair_cam", "pair_lidar") if pair else ("cwd_cam", "cwd_lidar")
+        tau = None if pair else float(feature_loss.tau)
         for i, key in enumerate(("camera_feat", "lidar_feat")):
             a, b = student_mids[key], teacher_mids[key]
-            _check_cwd_pair(a, b)
+            if pair:
+                _check_pair_pair(a, b)
+            else:
+                _check_cwd_pair(a, b)
             am, geom = ops.nhwc_view(a.detach())
             bm, _ = ops.nhwc_view(b.detach())
             want = beta != 0.0 and a.requires_grad
             da = torch.empty_like(am) if want else None
-            gcoef = float(np.float32(tau / (geom[0] * am.shape[1])) * np.float32(beta))     # the product the autograd form's backward forms
-            _cwd_call(am, bm, geom, tau, gcoef, None, vals[4 + i:5 + i], da)
+            if pair:
+                gcoef = float(np.float32(_pair_gcoef(geom)) * np.float32(beta))             # the product the autograd form's backward forms
+                _pair_call(am, bm, geom, gcoef, None, vals[4 + i:5 + i], da)
+            else:
+                gcoef = float(np.float32(tau / (geom[0] * am.shape[1])) * np.float32(beta))     # the product the autograd form's backward forms
+                _cwd_call(am, bm, geom, tau, gcoef, None, vals[4 + i:5 + i], da)
             if want:
                 gradsink.deposit(am, da)
         lib.call("kd_kd_total", P(hard), P(vals[4:5]), P(vals[5:6]), float(alpha * T * T), float(beta), P(vals[6:7]), stream())
@@ -628,7 +738,7 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
             gradsink.drop_pending()
             raise KDError("kd_objective_backward: a feature-map gradient was not collected by the fusion block's backward "
                           "(unsupported model structure for the fused objective; use kd_objective(...).backward())")
-        return vals[6], {"ce": hard[0], "kl": hard[1], "cwd_cam": vals[4], "cwd_lidar": vals[5], **extra}
+        return vals[6], {"ce": hard[0], "kl": hard[1], names[0]: vals[4], names[1]: vals[5], **extra}
     slabs, counts = [], []
     for key in ("camera_feat", "lidar_feat"):
         a, b = student_mids[key], teacher_mids[key]

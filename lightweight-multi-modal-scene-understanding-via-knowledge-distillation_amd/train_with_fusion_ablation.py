@@ -19,7 +19,9 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
   KD_FEATURE_LOSS   with KD_TEACHER: unset or `mse`: the feature MSE between the student's and the teacher's camera_feat / lidar_feat
                  maps.  `cwd`: channel-wise distillation in its place (kdrt.losses.ChannelKD: a temperature softmax over the
                  positions of every channel, KL to the teacher's) at temperature KD_CWD_TAU (4.0); beta keeps its meaning but
-                 the term's magnitude differs from the MSE's, so re-tune it
+                 the term's magnitude differs from the MSE's, so re-tune it.  `pair`: pair-wise distillation in Gram form
+                 (kdrt.losses.PairKD: the cosine similarities of all pairs of BEV positions against the teacher's, at full
+                 resolution, no parameter); re-tune beta here too (gradient entries of order 1e-7 before beta at 64 x 64)
   KD_EMA_DECAY   unset: off.  e.g. 0.999: keep an EMA of the weights inside the AdamW step; validation, best.pth and the
                  checkpoint's "ema_state" use it.  KD_EMA_WARMUP=1: d_t = min(decay, (1 + t) / (10 + t)).
                  KD_EMA_VALIDATE_LIVE=1 also validates the live weights (history "val_miou_live")
@@ -99,13 +101,16 @@ def hard_loss_from_env(env=os.environ):
 
 
 def feature_loss_from_env(env=os.environ):
-    """KD_FEATURE_LOSS -> None (unset or `mse`: the feature MSE) or ChannelKD(tau=KD_CWD_TAU, default 4.0) for `cwd`"""
+    """KD_FEATURE_LOSS -> None (unset or `mse`: the feature MSE), ChannelKD(tau=KD_CWD_TAU, default 4.0) for `cwd` or PairKD() for
+    `pair`"""
     name = env.get("KD_FEATURE_LOSS", "")
     if name in ("", "mse"):
         return None
-    if name != "cwd":
-        raise ValueError(f"KD_FEATURE_LOSS must be unset, 'mse' or 'cwd', got {name!r}")
-    from kdrt.losses import ChannelKD
+    if name not in ("cwd", "pair"):
+        raise ValueError(f"KD_FEATURE_LOSS must be unset, 'mse', 'cwd' or 'pair', got {name!r}")
+    from kdrt.losses import ChannelKD, PairKD
+    if name == "pair":
+        return PairKD()
     return ChannelKD(tau=float(env.get("KD_CWD_TAU", 4.0)))
 
 
