@@ -628,6 +628,31 @@ size_t kd_feat_pair_ws_bytes(int B, int HW, int Cs, int Ct);
 int kd_feat_pair_slices(int B, int HW);
 int kd_feat_pair_fwd_bwd(const float* s, const float* t, int B, int HW, int Cs, int Ct, float gcoef, const float* gscale_dev,
                          float* val, float* ds, float* img_vals_out, void* ws, size_t ws_bytes, void* stream);
+/* The opt-in intra-class feature variation distillation feature term (csrc/kd_loss_ifv.hip; Wang et al., ECCV 2020)
+ * of two NHWC feature matrices s [B*HW, Cs] and t [B*HW, Ct] under the label map target [B*HW] (int64, the maps' resolution).  Pixel i of
+ * image b is kept when target != ignore_index and 0 <= target < NC; K_b kept pixels, N_bc of class c.  For X in {s, t}, per image:
+ *   r_i = sqrt(sum_k x_ik^2), xh_i = x_i / r_i if r_i > 1e-12 else 0,  m_c = 1/N_bc sum_{i kept, y_i = c} x_i,
+ *   mh_c = m_c / |m_c| if |m_c| > 1e-12 else 0,  s_i = xh_i . mh_{y_i},
+ *   L_b = 1/K_b sum_{i kept} (sS_i - sT_i)^2 (0 for K_b = 0; the image still counts in B),  val[0] = IFV = 1/B sum_b L_b (not scaled),
+ *   ds_j = k * (w_j (mh_c - s_j xh_j) / r_j [0 for r_j <= 1e-12] + D_c / N_bc), c = y_j, w_i = (sS_i - sT_i) / K_b,
+ *          D_c = sum_{i kept, y_i = c} w_i (xh_i - s_i mh_c) / |m_c| (0 for |m_c| <= 1e-12), everything from s; 0 for a row that is not
+ *          kept; k = gcoef * (gscale_dev ? gscale_dev[0] : 1) formed once in fp32 (ds NULL: forward only).  That is k * (B/2) * dIFV/ds:
+ *          the caller passes gcoef = 2 / B times whatever it folds in.  A kept all-zero row still receives D_c / N_bc.
+ * img_vals_out (may be NULL; for tests): the B per-image values L_b.  kd_feat_ifv_slices(B, HW): the row slices an image is cut into
+ * (a function of B and HW alone; 0 for an unsupported B or HW).  Launches: per-class channel sums per (image, slice, map) in per-thread
+ * LDS accumulators; the slice join in double to m, |m|, mh, N_bc; the similarity pass (8 lanes per row, {1/r, sS, w} per pixel to the
+ * workspace); with ds the class sums of w_i xh_i; the per-image join in double (L_b, D_c / N_bc); the mean over images in one block;
+ * with ds the point-wise gradient pass.  No floating-point atomics, no host reads: capturable, bit-identical from call to call.  s and t
+ * go through the same instruction sequence: identical bits in both (s == t as pointers is allowed) give val[0] == 0 and ds == +-0.
+ * A width that is no multiple of 4 or outside 4..256, NC outside 2..16, HW < 1, HW > 2^30 or B < 1 is KD_ERR_SHAPE; a NULL s / t /
+ * target / val / ws or a gcoef that is not finite is KD_ERR_ARG; s, t, ds or ws not 16-byte aligned (target: 8) is KD_ERR_ALIGN;
+ * ws = kd_feat_ifv_ws_bytes(B, HW, Cs, Ct, NC) bytes (0 for an unsupported shape), else KD_ERR_WORKSPACE.  A refused call launches and
+ * writes nothing. */
+size_t kd_feat_ifv_ws_bytes(int B, int HW, int Cs, int Ct, int NC);
+int kd_feat_ifv_slices(int B, int HW);
+int kd_feat_ifv_fwd_bwd(const float* s, const float* t, const int64_t* target, int ignore_index, int B, int HW, int Cs, int Ct, int NC,
+                        float gcoef, const float* gscale_dev, float* val, float* ds, float* img_vals_out, void* ws, size_t ws_bytes,
+                        void* stream);
 /* pred[B*HW] = argmax over the NC (1..4) classes, first maximum wins; conf[M*M] (ACCUMULATED into) counts a pixel at [t, argmax]
  * when t != ignore_index and 0 <= t < M and argmax < M: M (1..4) is the width of the matrix, independent of NC.  Either of conf
  * and pred may be NULL; target NULL: no counting. */

@@ -14,7 +14,7 @@ import torch
 from . import gradsink, ops, units
 from .ddp import BucketedAllReduce
 from .lib import KDError
-from .losses import ChannelKD, LovaszLoss, OhemCE, PairKD, RegionLoss, kd_objective, kd_objective_backward
+from .losses import ChannelKD, IntraClassKD, LovaszLoss, OhemCE, PairKD, RegionLoss, kd_objective, kd_objective_backward
 from .optim import AccumCycle, FusedAdamW
 
 
@@ -25,13 +25,14 @@ class _TakesAccumSteps(type):
     """`KDStep(..., accum_steps=k, feature_loss=spec)`: keyword-only options taken here, so that KDStep.__init__ keeps the argument
     list callers and tests/test_gpu_region_loss.py pin, name for name.  accum_steps None (the default) takes the optimiser's value.
     feature_loss (kdrt.losses.ChannelKD): channel-wise distillation of the two feature maps in the feature MSE's place, or
-    (kdrt.losses.PairKD) pair-wise distillation in Gram form; None (the default) keeps the MSE and the calls it makes.  Both are
+    (kdrt.losses.PairKD) pair-wise distillation in Gram form, or (kdrt.losses.IntraClassKD) intra-class feature variation distillation
+    under the step's label map; None (the default) keeps the MSE and the calls it makes.  All are
     means over images: with equal shards the reducer's averaged gradient is the global batch's.  beta needs re-tuning when switching
-    (see ChannelKD, PairKD)."""
+    (see ChannelKD, PairKD, IntraClassKD)."""
 
     def __call__(cls, *args, accum_steps=None, feature_loss=None, **kw):
-        if feature_loss is not None and not isinstance(feature_loss, (ChannelKD, PairKD)):
-            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD, a kdrt.losses.PairKD or None, got {type(feature_loss).__name__}")
+        if feature_loss is not None and not isinstance(feature_loss, (ChannelKD, PairKD, IntraClassKD)):
+            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD, a kdrt.losses.PairKD, a kdrt.losses.IntraClassKD or None, got {type(feature_loss).__name__}")
         step = super().__call__(*args, **kw)
         step.feature_loss = feature_loss
         step.cycle = AccumCycle(step.opt, step.reducer, accum_steps)

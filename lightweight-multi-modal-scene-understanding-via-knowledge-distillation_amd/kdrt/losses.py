@@ -16,6 +16,9 @@
   pair_kd       : the opt-in pair-wise distillation feature term (PairKD; Liu et al., CVPR 2019) in the feature MSE's place: the cosine
                   similarities of all pairs of positions of a map against the teacher's, formed from C x C Gram matrices, never the
                   n x n affinities (csrc/kd_loss_pair.hip; definition in DESIGN.md section 3)
+  intra_class_kd : the opt-in intra-class feature variation distillation feature term (IntraClassKD; Wang et al., ECCV 2020) in the
+                  feature MSE's place: the cosine similarity of every labelled pixel to the prototype of its own class against the
+                  teacher's (csrc/kd_loss_ifv.hip; definition in DESIGN.md section 3)
   kd_objective  : CE + alpha*T^2*KL + beta*(MSE(cam) + MSE(lidar))   (the
                   reference has no KD code -- this definition is the build's specification)
   kd_objective_backward : the same objective AND its backward pass for the training step: every loss kernel
@@ -484,10 +487,40 @@ class PairKD:
 PAIR_MIN_C, PAIR_MAX_C = 4, 256   # csrc/kd_loss_pair.hip: widths in multiples of 4
 
 
+@dataclass(frozen=True)
+class IntraClassKD:
+    """Intra-class feature variation distillation (Wang et al., "Intra-class Feature Variation Distillation for Semantic
+    Segmentation", ECCV 2020) as the feature term of the KD objective, in the feature MSE's place.  S [B, n, Cs]
+    and T [B, n, Ct] are the NHWC matrices of the student's and the teacher's map, n = H*W, y [B, n] the label map at the maps'
+    resolution and NC the number of classes (the logits' class count).  Pixel i of image b is kept when y != ignore_index and
+    0 <= y < NC; K_b kept pixels, N_bc of class c.  For X in {S, T}, per image:
+
+      r_i   = sqrt(sum_k x_ik^2),  xh_i = x_i / r_i  if r_i > 1e-12, else 0
+      m_c   = 1/N_bc * sum_{i kept, y_i = c} x_i       the prototype of class c (classes with N_bc = 0 are absent)
+      mh_c  = m_c / |m_c|  if |m_c| > 1e-12, else 0
+      s_i   = xh_i . mh_{y_i}                           the cosine similarity of a kept pixel to its own class's prototype
+      L_b   = 1/K_b * sum_{i kept} (sS_i - sT_i)^2      (0 if K_b = 0; the image still counts in B)
+      IFV   = 1/B * sum_b L_b
+      g_i   = 2 (sS_i - sT_i) / (B K_b),   D_c = sum_{i kept, y_i = c} g_i (xh_i - s_i mh_c) / |m_c|        (all from S)
+      dIFV/dS_j = g_j (mh_c - s_j xh_j) / r_j + D_c / N_bc,  c = y_j, for kept j; 0 for a pixel that is not kept
+
+    A kept all-zero row still receives D_c / N_bc: the prototype is linear in it.  The compared quantity is one scalar per pixel:
+    no adapter, no parameter, and the two widths need not be equal (multiples of 4 from 4 to 256), 2 to 16 classes.  It is the one
+    feature term that reads the labels: where most BEV cells are background, the label-blind terms spend their gradient there.
+    beta keeps its meaning, but the term's magnitude is not the MSE's (a mean of squared cosine differences, at most 4) -- re-tune
+    beta when switching.
+    The term is a mean over images: with equal shards under data parallelism the mean of the per-rank values IS the value of the
+    global batch and the reducer's averaged gradient its gradient."""
+
+
+IFV_MIN_C, IFV_MAX_C = 4, 256     # csrc/kd_loss_ifv.hip: widths in multiples of 4
+IFV_MIN_NC, IFV_MAX_NC = 2, 16
+
+
 def _check_feature_spec(spec):
-    if not isinstance(spec, (ChannelKD, PairKD)):
-        raise KDError("the feature loss must be a kdrt.losses.ChannelKD or kdrt.losses.PairKD (or None for the feature MSE), got "
-                      f"{type(spec).__name__}")
+    if not isinstance(spec, (ChannelKD, PairKD, IntraClassKD)):
+        raise KDError("the feature loss must be a kdrt.losses.ChannelKD, kdrt.losses.PairKD or kdrt.losses.IntraClassKD (or None for "
+                      f"the feature MSE), got {type(spec).__name__}")
 
 
 def _check_cwd_pair(a, b):
@@ -605,6 +638,78 @@ def pair_kd(student_feat, teacher_feat):
     return _PairKDFn.apply(student_feat, teacher_feat)
 
 
+def _check_ifv_args(a, b, target, num_classes):
+    """the kernel indexes the maps as [B*H*W, Cs] and [B*H*W, Ct] and the labels as [B*H*W]: one B, H, W for all three"""
+    if not torch.is_tensor(a) or not torch.is_tensor(b) or not torch.is_tensor(target) or a.dim() != 4 or b.dim() != 4:
+        raise KDError("intra_class_kd: two [B, C, H, W] tensors and a [B, H, W] label map expected")
+    ops.require_gpu_tensor(a, "intra_class_kd")
+    if a.device != b.device or a.shape[0] != b.shape[0] or tuple(a.shape[2:]) != tuple(b.shape[2:]):
+        raise KDError(f"intra_class_kd: student map {tuple(a.shape)} on {a.device} and teacher map {tuple(b.shape)} on {b.device} must "
+                      "share B, H, W and the device")
+    B, _, H, W = a.shape
+    if tuple(target.shape) != (B, H, W) or target.device != a.device:
+        raise KDError(f"intra_class_kd: label map {tuple(target.shape)} on {target.device} does not match the feature maps' [B, H, W] = "
+                      f"{(B, H, W)} on {a.device} (the term needs labels at the maps' resolution: output_mode=\"same\")")
+    if target.dtype != torch.int64:
+        raise KDError(f"intra_class_kd: the label map must be int64, got {target.dtype}")
+    for C in (a.shape[1], b.shape[1]):
+        if C % 4 != 0 or C < IFV_MIN_C or C > IFV_MAX_C:
+            raise KDError(f"intra_class_kd: {C} channels unsupported (a multiple of 4 from {IFV_MIN_C} to {IFV_MAX_C})")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise KDError(f"intra_class_kd: fp32 maps expected, got {a.dtype} and {b.dtype}")
+    if int(num_classes) != num_classes or not IFV_MIN_NC <= num_classes <= IFV_MAX_NC:
+        raise KDError(f"intra_class_kd: {num_classes} classes unsupported ({IFV_MIN_NC} to {IFV_MAX_NC})")
+
+
+def _ifv_call(am, bm, target, geom, NC, ignore_index, gcoef, gdev, val, ds):
+    """one kd_feat_ifv_fwd_bwd call on the NHWC matrices am [B*H*W, Cs], bm [B*H*W, Ct] and the labels [B, H, W]: val[0] = IFV,
+    ds = gcoef * gdev[0] * (B / 2) * dIFV/dS"""
+    B, H, W = geom
+    Cs, Ct = am.shape[1], bm.shape[1]
+    nbytes = lib.kd_feat_ifv_ws_bytes(B, H * W, Cs, Ct, NC)
+    ws = ops.workspace(nbytes, am.device)
+    lib.call("kd_feat_ifv_fwd_bwd", P(am), P(bm), P(target), int(ignore_index), B, H * W, Cs, Ct, NC, float(gcoef), P(gdev), P(val), P(ds),
+             None, P(ws), nbytes, stream())
+
+
+def _ifv_gcoef(geom):
+    """2 / B, the host's double rounded to fp32 by the call"""
+    return 2.0 / float(geom[0])
+
+
+class _IntraClassKDFn(torch.autograd.Function):
+    """_PairKDFn's shape: forward the value only; backward one more call with the upstream gradient read from device memory, so the
+    gradient coefficient is k = fl32(fl32(2 / B) * g) -- with g = fl32(beta) from the objective's autograd graph the product
+    kd_objective_backward folds into gcoef on the host."""
+
+    @staticmethod
+    def forward(ctx, a, b, target, NC, ignore_index):
+        _check_ifv_args(a, b, target, NC)
+        am, geom = ops.nhwc_view(a.detach())
+        bm, _ = ops.nhwc_view(b.detach())
+        target = target.contiguous()
+        val = torch.empty(1, device=a.device, dtype=torch.float32)
+        _ifv_call(am, bm, target, geom, NC, ignore_index, 0.0, None, val, None)
+        ctx.am, ctx.bm, ctx.target, ctx.geom, ctx.NC, ctx.ignore_index = am, bm, target, geom, NC, ignore_index
+        return val[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        am, bm, geom = ctx.am, ctx.bm, ctx.geom
+        ds = torch.empty_like(am)
+        val = torch.empty(1, device=am.device, dtype=torch.float32)
+        _ifv_call(am, bm, ctx.target, geom, ctx.NC, ctx.ignore_index, _ifv_gcoef(geom), g.contiguous().view(1), val, ds)
+        return ops.nchw_from_matrix(ds, geom), None, None, None, None
+
+
+def intra_class_kd(student_feat, teacher_feat, target, num_classes, ignore_index=-1):
+    """IFV(student_feat, teacher_feat; target) of two fp32 maps [B, Cs, H, W] and [B, Ct, H, W] under the int64 label map [B, H, W] with
+    `num_classes` classes (see IntraClassKD): a device scalar whose gradient flows to the student map only.  KDError, before any
+    launch, on CPU tensors, a dtype other than fp32 / int64, differing B, H, W or devices (a label map of another size included), a
+    width that is no multiple of 4 or outside 4..256, and a class count outside 2..16."""
+    return _IntraClassKDFn.apply(student_feat, teacher_feat, target, int(num_classes), int(ignore_index))
+
+
 def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
                  class_weights=None, T: float = 4.0, alpha: float = 1.0, beta: float = 1.0, ignore_index: int = -1,
                  feature_loss=None, hard_loss=None):
@@ -618,10 +723,16 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
     feature_loss (a ChannelKD): beta * (CWD(camera_feat) + CWD(lidar_feat)) at its tau takes the two MSEs' place and parts carries
     "cwd_cam" / "cwd_lidar" instead of "mse_cam" / "mse_lidar".  A mean over images as well.  beta needs re-tuning (see ChannelKD).
     feature_loss (a PairKD): beta * (PAIR(camera_feat) + PAIR(lidar_feat)) takes the two MSEs' place and parts carries "pair_cam" /
-    "pair_lidar".  A mean over images as well.  beta needs re-tuning (see PairKD)."""
+    "pair_lidar".  A mean over images as well.  beta needs re-tuning (see PairKD).
+    feature_loss (an IntraClassKD): beta * (IFV(camera_feat) + IFV(lidar_feat)) under `target` with the logits' class count takes the
+    two MSEs' place and parts carries "ifv_cam" / "ifv_lidar".  The label map must have the feature maps' H x W.  A mean over images
+    as well.  beta needs re-tuning (see IntraClassKD)."""
     extra = {}
     if feature_loss is not None:
         _check_feature_spec(feature_loss)
+        if isinstance(feature_loss, IntraClassKD):                # before any launch
+            for key in ("camera_feat", "lidar_feat"):
+                _check_ifv_args(student_mids[key], teacher_mids[key], target, student_logits.shape[1])
     if hard_loss is None:
         ce, kl = seg_loss(student_logits, target, class_weights, ignore_index, teacher_logits, T, alpha)
     elif isinstance(hard_loss, OhemCE):
@@ -640,6 +751,11 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
         names = ("pair_cam", "pair_lidar")
         mse_c = pair_kd(student_mids["camera_feat"], teacher_mids["camera_feat"])
         mse_l = pair_kd(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
+    elif isinstance(feature_loss, IntraClassKD):
+        names = ("ifv_cam", "ifv_lidar")
+        NC = student_logits.shape[1]
+        mse_c = intra_class_kd(student_mids["camera_feat"], teacher_mids["camera_feat"], target, NC, ignore_index)
+        mse_l = intra_class_kd(student_mids["lidar_feat"], teacher_mids["lidar_feat"], target, NC, ignore_index)
     else:
         names = ("cwd_cam", "cwd_lidar")
         mse_c = channel_kd(student_mids["camera_feat"], teacher_mids["camera_feat"], feature_loss.tau)
@@ -664,6 +780,8 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     deposited exactly as the MSE's is, and kd_kd_total forms the total from the two values ("cwd_cam" / "cwd_lidar").
     feature_loss (a PairKD): the same with ONE kd_feat_pair_fwd_bwd call per map and gcoef = fl32(fl32(4 / (B n^2)) * fl32(beta))
     ("pair_cam" / "pair_lidar").
+    feature_loss (an IntraClassKD): the same with ONE kd_feat_ifv_fwd_bwd call per map and gcoef = fl32(fl32(2 / B) * fl32(beta))
+    ("ifv_cam" / "ifv_lidar"); a label map that has not the feature maps' H x W is refused before the first launch.
 
     Same values and the same gradient bits as the autograd formulation, fewer passes: the segmentation-loss call writes
     dL/dlogits together with CE / KL; each feature MSE writes its gradient in the pass that sums its value, and that
@@ -682,6 +800,11 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     _check_target(zs_c, target)
     _check_class_weights(zs_c, class_weights)
     B, NC, H, W = zs_c.shape
+    if feature_loss is not None:
+        _check_feature_spec(feature_loss)
+        if isinstance(feature_loss, IntraClassKD):                # before any launch
+            for key in ("camera_feat", "lidar_feat"):
+                _check_ifv_args(student_mids[key], teacher_mids[key], target, NC)
     vals = torch.empty(8, device=dev, dtype=torch.float32)        # [0:4] seg-loss values, [4] mse_cam, [5] mse_lidar, [6] total
     dzs = torch.empty_like(zs_c)
     nbytes = lib.kd_seg_loss_ws_bytes(B * H * W)
@@ -711,14 +834,14 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     gradsink.drop_pending()
     if feature_loss is not None:
         _check_feature_spec(feature_loss)
-        pair = isinstance(feature_loss, PairKD)
-        names = ("pair_cam", "pair_lidar") if pair else ("cwd_cam", "cwd_lidar")
-        tau = None if pair else float(feature_loss.tau)
+        pair, ifv = isinstance(feature_loss, PairKD), isinstance(feature_loss, IntraClassKD)
+        names = ("pair_cam", "pair_lidar") if pair else ("ifv_cam", "ifv_lidar") if ifv else ("cwd_cam", "cwd_lidar")
+        tau = None if pair or ifv else float(feature_loss.tau)
         for i, key in enumerate(("camera_feat", "lidar_feat")):
             a, b = student_mids[key], teacher_mids[key]
             if pair:
                 _check_pair_pair(a, b)
-            else:
+            elif not ifv:
                 _check_cwd_pair(a, b)
             am, geom = ops.nhwc_view(a.detach())
             bm, _ = ops.nhwc_view(b.detach())
@@ -727,6 +850,9 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
             if pair:
                 gcoef = float(np.float32(_pair_gcoef(geom)) * np.float32(beta))             # the product the autograd form's backward forms
                 _pair_call(am, bm, geom, gcoef, None, vals[4 + i:5 + i], da)
+            elif ifv:
+                gcoef = float(np.float32(_ifv_gcoef(geom)) * np.float32(beta))              # the product the autograd form's backward forms
+                _ifv_call(am, bm, target, geom, NC, ignore_index, gcoef, None, vals[4 + i:5 + i], da)
             else:
                 gcoef = float(np.float32(tau / (geom[0] * am.shape[1])) * np.float32(beta))     # the product the autograd form's backward forms
                 _cwd_call(am, bm, geom, tau, gcoef, None, vals[4 + i:5 + i], da)

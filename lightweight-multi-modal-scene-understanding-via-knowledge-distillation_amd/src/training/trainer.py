@@ -23,7 +23,7 @@ from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
 from kdrt.lib import KDError
-from kdrt.losses import ChannelKD, LovaszLoss, OhemCE, PairKD, RegionLoss, confusion, lovasz_seg_loss, ohem_seg_loss, region_seg_loss, seg_loss
+from kdrt.losses import ChannelKD, IntraClassKD, LovaszLoss, OhemCE, PairKD, RegionLoss, confusion, lovasz_seg_loss, ohem_seg_loss, region_seg_loss, seg_loss
 from kdrt.optim import AccumCycle, FusedAdamW, check_accum_steps, decay_groups
 
 try:
@@ -389,13 +389,14 @@ class Trainer(metaclass=_TakesNumClasses):
 class KDTrainer(Trainer):
     """Teacher -> student distillation on top of `Trainer`.  total = CE + alpha*T^2*KL + beta*(MSE(camera_feat)
     + MSE(lidar_feat)) (`hard_loss=RegionLoss(...)`: focal + Tversky in the CE's place; `feature_loss=ChannelKD(tau)`: channel-wise
-    distillation of the two feature maps in the MSEs' place, `feature_loss=PairKD()`: pair-wise distillation in Gram form, training only -- validation reports the hard-label loss -- and beta
+    distillation of the two feature maps in the MSEs' place, `feature_loss=PairKD()`: pair-wise distillation in Gram form,
+    `feature_loss=IntraClassKD()`: intra-class feature variation distillation under the labels, training only -- validation reports the hard-label loss -- and beta
     needs re-tuning); the teacher runs in eval mode under no_grad.  With torch.distributed initialised the
     student is broadcast from rank 0 and gradients are all-reduced in buckets overlapped with backward."""
 
     def __init__(self, model, teacher, train_loader, val_loader, device, T=4.0, alpha=1.0, beta=1.0, feature_loss=None, **kw):
-        if feature_loss is not None and not isinstance(feature_loss, (ChannelKD, PairKD)):
-            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD, a kdrt.losses.PairKD or None, got {type(feature_loss).__name__}")
+        if feature_loss is not None and not isinstance(feature_loss, (ChannelKD, PairKD, IntraClassKD)):
+            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD, a kdrt.losses.PairKD, a kdrt.losses.IntraClassKD or None, got {type(feature_loss).__name__}")
         super().__init__(model, train_loader, val_loader, device, **kw)
         self.teacher = teacher
         if distributed():

@@ -21,7 +21,10 @@ Environment knobs (defaults reproduce the reference's literals, train_with_fusio
                  positions of every channel, KL to the teacher's) at temperature KD_CWD_TAU (4.0); beta keeps its meaning but
                  the term's magnitude differs from the MSE's, so re-tune it.  `pair`: pair-wise distillation in Gram form
                  (kdrt.losses.PairKD: the cosine similarities of all pairs of BEV positions against the teacher's, at full
-                 resolution, no parameter); re-tune beta here too (gradient entries of order 1e-7 before beta at 64 x 64)
+                 resolution, no parameter); re-tune beta here too (gradient entries of order 1e-7 before beta at 64 x 64).  `ifv`:
+                 intra-class feature variation distillation (kdrt.losses.IntraClassKD: the cosine similarity of every labelled BEV
+                 cell to the prototype of its own class against the teacher's; reads the label map, 2 to 16 classes, no
+                 parameter); re-tune beta here too
   KD_EMA_DECAY   unset: off.  e.g. 0.999: keep an EMA of the weights inside the AdamW step; validation, best.pth and the
                  checkpoint's "ema_state" use it.  KD_EMA_WARMUP=1: d_t = min(decay, (1 + t) / (10 + t)).
                  KD_EMA_VALIDATE_LIVE=1 also validates the live weights (history "val_miou_live")
@@ -101,14 +104,16 @@ def hard_loss_from_env(env=os.environ):
 
 
 def feature_loss_from_env(env=os.environ):
-    """KD_FEATURE_LOSS -> None (unset or `mse`: the feature MSE), ChannelKD(tau=KD_CWD_TAU, default 4.0) for `cwd` or PairKD() for
-    `pair`"""
+    """KD_FEATURE_LOSS -> None (unset or `mse`: the feature MSE), ChannelKD(tau=KD_CWD_TAU, default 4.0) for `cwd`, PairKD() for
+    `pair` or IntraClassKD() for `ifv`"""
     name = env.get("KD_FEATURE_LOSS", "")
     if name in ("", "mse"):
         return None
-    if name not in ("cwd", "pair"):
-        raise ValueError(f"KD_FEATURE_LOSS must be unset, 'mse', 'cwd' or 'pair', got {name!r}")
-    from kdrt.losses import ChannelKD, PairKD
+    if name not in ("cwd", "pair", "ifv"):
+        raise ValueError(f"KD_FEATURE_LOSS must be unset, 'mse', 'cwd', 'pair' or 'ifv', got {name!r}")
+    from kdrt.losses import ChannelKD, IntraClassKD, PairKD
+    if name == "ifv":
+        return IntraClassKD()
     if name == "pair":
         return PairKD()
     return ChannelKD(tau=float(env.get("KD_CWD_TAU", 4.0)))
