@@ -49,23 +49,48 @@ def teacher_state():
     return O.randomize_state(state_template("concat"), TEACHER_SEED)
 
 
+def build_model(fusion, num_classes=2, base=32, grid=None):
+    """the product model of the step tests on the CPU: TwinLite camera encoder of width `base`, spatial LiDAR encoder on a
+    grid x grid BEV (default G), FPN over stages 3 - 5, same-resolution head"""
+    from src.models.camera_encoder import TwinLiteEncoder
+    from src.models.fusion_module import CompleteSegmentationModel
+    from src.models.lidar_encoder import LiDAREncoder
+    from _gpu_util import FUSIONS
+    cam = TwinLiteEncoder(base_channels=base, return_multiscale=True)
+    lid = LiDAREncoder(encoder_type="spatial", grid_size=(grid or G, grid or G), use_vectorized=True)
+    return CompleteSegmentationModel(cam, lid, num_classes=num_classes, fusion_type=fusion, fusion_out_channels=FUSIONS[fusion],
+                                     camera_fpn_stages=["stage3", "stage4", "stage5"], camera_fpn_channels=128, output_mode="same")
+
+
+def random_state(model, seed):
+    """kd_oracle.randomize_state over the model's own names and shapes (the recipe of _gpu_util.load_random_state)"""
+    sd = model.state_dict()
+    st = O.randomize_state({k: v.detach().cpu().clone() for k, v in sd.items()}, seed)
+    for k, v in sd.items():
+        if k.endswith("grid_tensor"):
+            st[k] = v.detach().cpu().clone()
+    return st
+
+
 def _cast(st, dtype):
     return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in st.items()}
 
 
-def oracle_step(objective, fusion, state, batch, dtype, t_state=None):
+def oracle_step(objective, fusion, state, batch, dtype, t_state=None, kd_objective=None, cw=CW, grid=G):
     """Forward, loss and backward of one step from `state` (a name-keyed CPU state_dict; not modified) in `dtype`.
     -> {"parts": {name: float}, "logits", "grads": {name: tensor}, "state": the state after the forward pass (BatchNorm running
-    statistics and num_batches_tracked updated)}.  The same calls in the same order as _gpu_util.fp64_oracle_grads."""
+    statistics and num_batches_tracked updated)}.  The same calls in the same order as _gpu_util.fp64_oracle_grads.
+    kd_objective: a callable with kd_oracle.kd_loss's signature in its place (tests/_fp64_objective_ref.step_objective: the KD
+    objective under a hard_loss / feature_loss option); cw, grid: the class weights and the BEV grid of a case that has its own."""
     images, pts, labels = batch
-    cw = torch.tensor(CW)
+    cw = torch.tensor(cw)
     s = O.clone_state(_cast(state, dtype), requires_grad=True)
-    zs, ms = O.complete_model(images.to(dtype), pts.to(dtype), s, fusion_type=fusion, grid=(G, G), training=True)
+    zs, ms = O.complete_model(images.to(dtype), pts.to(dtype), s, fusion_type=fusion, grid=(grid, grid), training=True)
     if objective == "kd":
         t = _cast(teacher_state() if t_state is None else t_state, dtype)
         with torch.no_grad():
-            zt, mt = O.complete_model(images.to(dtype), pts.to(dtype), t, fusion_type="concat", grid=(G, G), training=False)
-        total, parts = O.kd_loss(zs, ms, zt, mt, labels, cw.to(dtype), T, ALPHA, BETA)
+            zt, mt = O.complete_model(images.to(dtype), pts.to(dtype), t, fusion_type="concat", grid=(grid, grid), training=False)
+        total, parts = (O.kd_loss if kd_objective is None else kd_objective)(zs, ms, zt, mt, labels, cw.to(dtype), T, ALPHA, BETA)
         parts = {k: v.item() for k, v in parts.items()}
     else:
         total, parts = O.weighted_ce(zs, labels, cw.to(dtype)), {}

@@ -230,13 +230,6 @@ def test_kd_step_eager_and_graphed():
         assert bool(torch.isfinite(p_e[k])) and _same_bits(p_e[k], p_g[k]), k
 
 
-def test_with_lovasz_hard_loss():
-    from kdrt.losses import ChannelKD, LovaszLoss
-    p, g, w = _kd_step(1e-3, steps=2, feature_loss=ChannelKD(), hard_loss=LovaszLoss())
-    assert set(p) == PARTS | {"lovasz"}
-    assert all(bool(torch.isfinite(p[k])) for k in p) and bool(torch.isfinite(g).all()) and bool(torch.isfinite(w).all())
-
-
 def test_default_path_is_untouched_by_the_option(monkeypatch):
     """feature_loss=None and no argument at all leave the same parameter bytes, before and after a channel-KD step has run in
     the process, and make the library calls of the MSE objective: no channel-KD entry point, the parent commit's loss calls"""

@@ -68,6 +68,13 @@ def _case(shape):
     return _CACHE[shape]
 
 
+def _bounds(ref, f32):
+    """(value, per-image values, gradient elements): 4 x the float32 evaluation's own distance from float64 + 8 U x the magnitude that
+    cancels (tests/test_gpu_objective_matrix.py applies the same bounds to the term inside the KD objective)"""
+    ev32, ei32, eg32 = (f32["val"] - ref["val"]).abs().item(), (f32["img"] - ref["img"]).abs(), (f32["grad"] - ref["grad"]).abs().max().item()
+    return 4 * ev32 + 8 * V.U * ref["Sv"].item(), 4 * ei32 + 8 * V.U * ref["Sv_img"], 4 * eg32 + 8 * V.U * ref["M"]
+
+
 def _float64_shape(shape):
     """-> the list of what is outside its bound for one shape (empty: inside), after printing every figure"""
     lib, _, _ = _lib()
@@ -92,9 +99,7 @@ def _float64_shape(shape):
     v64, g64 = ref["val"], ref["grad"]
     ev32, ei32, eg32 = (y32["val"] - v64).abs().item(), (y32["img"] - ref["img"]).abs(), (y32["grad"] - g64).abs().max().item()
     ev, ei, eg = abs(val.t[0].double().item() - v64.item()), (ib.t.double() - ref["img"]).abs(), (ds.t.double() - g64).abs()
-    bound_v = 4 * ev32 + 8 * V.U * ref["Sv"].item()
-    bound_i = 4 * ei32 + 8 * V.U * ref["Sv_img"]
-    bound_g = 4 * eg32 + 8 * V.U * ref["M"]
+    bound_v, bound_i, bound_g = _bounds(ref, y32)
     gmax = g64.abs().max().item()
     line = (f"ifv {_id(shape)}: val {val.t[0].item():.9g} float64 {v64.item():.9g} |d| {ev:.3g} ifv32 {ev32:.3g} |d|/bound {ev / max(bound_v, 1e-300):.3g}"
             f" | img worst |d|/bound {(ei / bound_i.clamp_min(1e-300)).max().item():.3g}"

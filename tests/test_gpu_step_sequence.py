@@ -26,25 +26,7 @@ MAX_GRAD_NORM = 1.0                                        # far below the gradi
 _TEACHER_STATES = {}
 
 
-def _build(fusion, num_classes=2, base=32):
-    from src.models.camera_encoder import TwinLiteEncoder
-    from src.models.fusion_module import CompleteSegmentationModel
-    from src.models.lidar_encoder import LiDAREncoder
-    from _gpu_util import FUSIONS
-    cam = TwinLiteEncoder(base_channels=base, return_multiscale=True)
-    lid = LiDAREncoder(encoder_type="spatial", grid_size=(R.G, R.G), use_vectorized=True)
-    return CompleteSegmentationModel(cam, lid, num_classes=num_classes, fusion_type=fusion, fusion_out_channels=FUSIONS[fusion],
-                                     camera_fpn_stages=["stage3", "stage4", "stage5"], camera_fpn_channels=128, output_mode="same")
-
-
-def _random_state(model, seed):
-    """kd_oracle.randomize_state over the model's own names and shapes (the recipe of _gpu_util.load_random_state)"""
-    sd = model.state_dict()
-    st = O.randomize_state({k: v.detach().cpu().clone() for k, v in sd.items()}, seed)
-    for k, v in sd.items():
-        if k.endswith("grid_tensor"):
-            st[k] = v.detach().cpu().clone()
-    return st
+_build, _random_state = R.build_model, R.random_state
 
 
 def _clone(x):
@@ -63,17 +45,31 @@ def _batch(seed, num_classes=2):
     return images.cuda(), pts.cuda(), labels.cuda()
 
 
+def _graphed_cycle(graphed, batches):
+    """One replay of a GraphedKDStep captured over an accumulation cycle, in the shape of the eager cycle's last call.  The contract
+    of GraphedKDStep this mirrors (kdrt/kd.py, its class docstring and _body): a graph over accum_steps = k takes the k * B frames of
+    the cycle in ONE call; of the returned parts "logits" covers all k * B frames (the eager call: the last B), "total" is the mean of
+    the k micro-batch losses (the eager side forms the same mean when Rig.cycle_total is set) and "grad_norm" is inserted before
+    "stepped" (the eager step: after it).  Everything else is the last micro-batch's, as in the eager cycle."""
+    parts = dict(graphed(*(torch.cat(t) for t in zip(*batches))))
+    tail = {k: parts.pop(k) for k in ("grad_norm", "total", "logits") if k in parts}      # the eager step's key order
+    parts.update(tail)
+    parts["logits"] = parts["logits"][-batches[-1][0].shape[0]:]
+    torch.cuda.synchronize()
+    return parts
+
+
 class Rig:
     """student + FusedAdamW + step object (+ teacher) of one case.  `fresh=True`: nothing is initialised beyond the constructors'
     defaults -- the state comes from load()."""
 
     def __init__(self, objective="kd", fusion="weighted", fresh=False, num_classes=2, base=32, opt_kw=None, groups=False,
-                 step_kw=None):
+                 step_kw=None, cycle_total=False, grid=None):
         from kdrt import gradsink
         from kdrt.kd import KDStep
         from kdrt.optim import AccumCycle, FusedAdamW, decay_groups
-        self.objective, self.num_classes = objective, num_classes
-        self.student = _build(fusion, num_classes, base)
+        self.objective, self.num_classes, self.cycle_total = objective, num_classes, cycle_total
+        self.student = _build(fusion, num_classes, base, grid)
         if not fresh:
             self.student.load_state_dict(_random_state(self.student, R.STUDENT_SEED))
         self.student = self.student.cuda().train()
@@ -86,10 +82,10 @@ class Rig:
         self.cw = torch.tensor(list(R.CW) if num_classes == 2 else CW8).cuda()
         self.teacher = None
         if objective == "kd":
-            self.teacher = _build("concat", num_classes)
-            if num_classes not in _TEACHER_STATES:
-                _TEACHER_STATES[num_classes] = _random_state(self.teacher, R.TEACHER_SEED)
-            self.teacher.load_state_dict(_TEACHER_STATES[num_classes])
+            self.teacher = _build("concat", num_classes, grid=grid)
+            if (num_classes, grid) not in _TEACHER_STATES:
+                _TEACHER_STATES[num_classes, grid] = _random_state(self.teacher, R.TEACHER_SEED)
+            self.teacher.load_state_dict(_TEACHER_STATES[num_classes, grid])
             self.teacher = self.teacher.cuda().eval()
             self.step = KDStep(self.student, self.teacher, self.opt, self.cw, T=R.T, alpha=R.ALPHA, beta=R.BETA, **(step_kw or {}))
         else:                                              # the sequence of Trainer._step, as _gpu_util.fp64_gpu_grads writes it out
@@ -114,6 +110,9 @@ class Rig:
 
     def run(self, *batches):
         """one optimiser step: one batch, or the accum_steps micro-batches of a cycle -> the parts of the last call"""
+        if self.graphed is not None and len(batches) > 1:
+            return _graphed_cycle(self.graphed, batches)
+        totals = []
         for b in batches:
             if self.graphed is not None:
                 parts = self.graphed(*b)
@@ -121,6 +120,9 @@ class Rig:
                 parts = self.step(*b)
             else:
                 parts = self._ce_step(*b)
+            totals.append(parts["total"])
+        if self.cycle_total and len(batches) > 1:          # the eager side of _graphed_cycle: "total" as GraphedKDStep reports it
+            parts["total"] = torch.stack(totals).mean()
         torch.cuda.synchronize()
         return parts
 
@@ -239,10 +241,12 @@ def test_restart_equivalence_default_steps(case):
 
 
 def _option(name):
-    """-> (make(fresh), batches) of an option case: KDStep with the weighted student, one option at a time, the arguments of each
-    option's own test file"""
-    from kdrt.losses import ChannelKD, LovaszLoss, RegionLoss
+    """-> (make(fresh), batches) of an option case: KDStep with the weighted student, one option at a time (or one of the COMBINED
+    sets, names joined by "+"), the arguments of each option's own test file"""
+    from kdrt.losses import ChannelKD, IntraClassKD, LovaszLoss, OhemCE, PairKD, RegionLoss
     batches = _default_batches()
+    region = RegionLoss(gamma=2.0, wf=1.0, wt=0.8, a=0.7, b=0.3, s=1.0)
+    ohem = OhemCE(thresh=0.7, min_divisor=4, min_kept=8)
     if name == "clip":
         kw = dict(opt_kw={"max_grad_norm": MAX_GRAD_NORM})
     elif name == "groups_ema":
@@ -253,7 +257,7 @@ def _option(name):
     elif name == "cwd":
         kw = dict(step_kw={"feature_loss": ChannelKD()})
     elif name == "region":
-        kw = dict(step_kw={"hard_loss": RegionLoss(gamma=2.0, wf=1.0, wt=0.8, a=0.7, b=0.3, s=1.0)})
+        kw = dict(step_kw={"hard_loss": region})
     elif name == "lovasz":
         kw = dict(step_kw={"hard_loss": LovaszLoss(weight=0.7)})
     elif name == "classes8":
@@ -263,34 +267,81 @@ def _option(name):
         kw = dict(base=16)
     elif name == "bf16_teacher":
         kw = dict(step_kw={"teacher_storage": "bf16"})
+    elif name == "ohem":
+        kw = dict(step_kw={"hard_loss": ohem})
+    elif name == "pair":
+        kw = dict(step_kw={"feature_loss": PairKD()})
+    elif name == "ifv":                                    # the labels of _batch live on the G x G grid of both feature maps
+        kw = dict(step_kw={"feature_loss": IntraClassKD()})
+    elif name == "ohem+ifv+classes8+clip+accum2":
+        kw = dict(num_classes=NC8, opt_kw={"max_grad_norm": MAX_GRAD_NORM, "accum_steps": 2},
+                  step_kw={"hard_loss": ohem, "feature_loss": IntraClassKD()})
+        batches = [(_batch(s, NC8), _batch(s + 10, NC8)) for s in R.SEEDS]
+    elif name == "lovasz_region+pair+groups_ema":
+        kw = dict(groups=True, opt_kw={"ema_decay": 0.999, "ema_warmup": True},
+                  step_kw={"hard_loss": LovaszLoss(weight=1.5, base=region), "feature_loss": PairKD()})
     else:
         raise KeyError(name)
     return (lambda fresh: Rig("kd", "weighted", fresh, **kw)), batches
 
 
+COMBINED = ("ohem+ifv+classes8+clip+accum2", "lovasz_region+pair+groups_ema")
+NEWER = ("ohem", "pair", "ifv") + COMBINED                # run inside test_restart_equivalence_of_graph_replays: see there
+
+
 @pytest.mark.parametrize("option", ("clip", "groups_ema", "accum2", "cwd", "region", "lovasz", "classes8", "base16", "bf16_teacher"))
 def test_restart_equivalence_with_one_option(option):
+    _one_option(option)
+
+
+def _graph_replays(option):
+    """Replay k, fed batch k, against a fresh EAGER step from the checkpoint taken after replay k - 1.  The sequence starts after
+    the capture (three warm-up steps on another batch have moved the state by then).  The combined options capture their whole
+    objective (and, with accum2, a whole cycle of two micro-batches) on one batch and replay it on a new one each time."""
+    from kdrt import ops
+    from kdrt.kd import GraphedKDStep
+    if option == "default":
+        make, batches, nc = (lambda fresh: Rig("kd", "weighted", fresh)), _default_batches(), 2
+    else:
+        one, batches = _option(option)
+        nc = NC8 if "classes8" in option else 2
+
+        def make(fresh):
+            rig = one(fresh)
+            rig.cycle_total = True
+            return rig
+    L = make(False)
+    warm = tuple(torch.cat(t) for t in zip(*[_batch(4 + 10 * j, nc) for j in range(len(batches[0]))]))
+    L.graphed = GraphedKDStep(L.step, *warm, warmup=3)
+    table = L.graphed.transposes[0]
+    assert table is not None and table is ops.TRANSPOSES.table
+    results = restart_sequence(make, batches, long_lived=L, done=3)
+    _assert_restart_equal(results, "graphed " + option)
+    # the eager rigs registered their own weights meanwhile: the cache has another table, the graph still owns the one it replays
+    assert ops.TRANSPOSES.table is not table and L.graphed.transposes[0] is table and L.graphed.replays == R.K
+
+
+def _one_option(option):
     make, batches = _option(option)
     results = restart_sequence(make, batches)
     _assert_restart_equal(results, option)
-    if option == "clip":
+    if "clip" in option.split("+"):
         assert all(r[3] > MAX_GRAD_NORM for r in results), [r[3] for r in results]
 
 
 def test_restart_equivalence_of_graph_replays():
-    """Replay k, fed batch k, against a fresh EAGER step from the checkpoint taken after replay k - 1.  The sequence starts after
-    the capture (three warm-up steps on another batch have moved the state by then)."""
-    from kdrt import ops
-    from kdrt.kd import GraphedKDStep
-    L = Rig("kd", "weighted")
-    warm = _batch(4)
-    L.graphed = GraphedKDStep(L.step, *warm, warmup=3)
-    table = L.graphed.transposes[0]
-    assert table is not None and table is ops.TRANSPOSES.table
-    results = restart_sequence(lambda fresh: Rig("kd", "weighted", fresh), _default_batches(), long_lived=L, done=3)
-    _assert_restart_equal(results, "graphed")
-    # the eager rigs registered their own weights meanwhile: the cache has another table, the graph still owns the one it replays
-    assert ops.TRANSPOSES.table is not table and L.graphed.transposes[0] is table and L.graphed.replays == R.K
+    """Graph replays of the default step and of the two COMBINED option sets, each captured on one batch and replayed on a new batch
+    every time, against fresh eager steps; then the eager restart sequences of the NEWER options (OhemCE, PairKD, IntraClassKD and the
+    two combined sets), the body of test_restart_equivalence_with_one_option.  Every sequence runs whatever the others did, and the
+    assertion names each one that failed."""
+    failed = {}
+    for label, run, option in [("replays " + o, _graph_replays, o) for o in ("default",) + COMBINED] + [("eager " + o, _one_option, o) for o in NEWER]:
+        try:
+            run(option)
+        except Exception as e:
+            print("SEQUENCE FAILED:", label, repr(e)[:300])
+            failed[label] = repr(e)[:500]
+    assert not failed, failed
 
 
 def test_captured_eval_lidar_encoder_on_a_different_batch_per_replay():
