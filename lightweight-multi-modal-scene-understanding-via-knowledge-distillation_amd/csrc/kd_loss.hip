@@ -5,7 +5,7 @@
 //   * feature MSE forward + gradient;
 //   * argmax + confusion matrix (SegmentationMetrics.update, trainer.py:18-26) -- integer exact;
 //   * AdamW over flat parameter / gradient / moment buffers (trainer.py:56, torch.optim.AdamW math).
-#include "kd_common.h"
+#include "kd_loss_common.h"
 
 namespace {
 
@@ -18,21 +18,6 @@ struct SegArgs {
   float* slab; float* losses; float* dzs;
   int64_t npix; int HW; int NC;
 };
-
-// K: the class bucket.  Every per-class loop runs j = 0 .. K-1 in ascending order, fully unrolled, guarded by j < NC: the
-// per-pixel arrays stay in registers and the operation order is that of the K = 4 instance for every bucket.
-template <int K>
-__device__ __forceinline__ void softmax_c(const float* z, int NC, float invT, float* p, float* logp) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < K; ++j) if (j < NC) mx = fmaxf(mx, z[j] * invT);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < K; ++j) if (j < NC) { p[j] = expf(z[j] * invT - mx); s += p[j]; }
-  const float ls = logf(s);
-#pragma unroll
-  for (int j = 0; j < K; ++j) if (j < NC) { logp[j] = z[j] * invT - mx - ls; p[j] = p[j] / s; }
-}
 
 __device__ __forceinline__ void block_sum3(float a, float b, float c, float* out3) {
   __shared__ float red[3][4];
@@ -52,7 +37,7 @@ __global__ __launch_bounds__(256) void seg_loss_partial_kernel(SegArgs a) {
 #pragma unroll
     for (int j = 0; j < K; ++j) if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw];
     const int64_t y = a.target[i];
-    if (y != a.ignore_index && y >= 0 && y < a.NC) {
+    if (KD_KEPT_LABEL(y, a.ignore_index, a.NC)) {
       softmax_c<K>(z, a.NC, 1.f, p, lp);
       float nll = 0.f;
 #pragma unroll
@@ -102,7 +87,7 @@ __global__ __launch_bounds__(256) void seg_loss_grad_kernel(SegArgs a) {
 #pragma unroll
     for (int j = 0; j < K; ++j) { g[j] = 0.f; if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw]; }
     const int64_t y = a.target[i];
-    if (y != a.ignore_index && y >= 0 && y < a.NC) {
+    if (KD_KEPT_LABEL(y, a.ignore_index, a.NC)) {
       softmax_c<K>(z, a.NC, 1.f, p, lp);
       const float w = (a.cw ? a.cw[y] : 1.f) * gs / sumw;
 #pragma unroll
@@ -268,15 +253,9 @@ int kd_seg_loss_fwd_bwd(const float* zs, const float* zt, const int64_t* target,
   SegArgs a{zs, zt, target, class_w, ignore_index, T, alpha, gscale, gscale_dev, (float*)ws, losses, dzs, npix, HW, NC};
   hipStream_t st = (hipStream_t)stream;
   const dim3 g((unsigned)grid), blk(256);
-  if (NC <= 4) hipLaunchKernelGGL(seg_loss_partial_kernel<4>, g, blk, 0, st, a);
-  else if (NC <= 8) hipLaunchKernelGGL(seg_loss_partial_kernel<8>, g, blk, 0, st, a);
-  else hipLaunchKernelGGL(seg_loss_partial_kernel<16>, g, blk, 0, st, a);
+  KD_LAUNCH_CLASS_BUCKET(seg_loss_partial_kernel, NC, g, blk, st, a);
   hipLaunchKernelGGL(seg_loss_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, (int)grid, (double)npix, losses);
-  if (dzs) {
-    if (NC <= 4) hipLaunchKernelGGL(seg_loss_grad_kernel<4>, g, blk, 0, st, a);
-    else if (NC <= 8) hipLaunchKernelGGL(seg_loss_grad_kernel<8>, g, blk, 0, st, a);
-    else hipLaunchKernelGGL(seg_loss_grad_kernel<16>, g, blk, 0, st, a);
-  }
+  if (dzs) KD_LAUNCH_CLASS_BUCKET(seg_loss_grad_kernel, NC, g, blk, st, a);
   return kd_check_launch("kd_seg_loss_fwd_bwd");
 }
 

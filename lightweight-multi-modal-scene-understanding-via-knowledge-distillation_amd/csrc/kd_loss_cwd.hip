@@ -12,7 +12,7 @@
 // No atomics, a fixed order everywhere, and s and t go through the same device functions operation for operation (every product
 // that could contract with a neighbouring sum is an explicit __fmul_rn / fmaf): identical bits in s and t give val == 0 and
 // ds == +-0, and an image's statistics and gradient depend on that image's rows alone.
-#include "kd_common.h"
+#include "kd_loss_common.h"
 
 #include <cmath>
 
@@ -58,9 +58,6 @@ struct CwdArgs {
 
 struct MS4 { float4 m, s; };
 
-__device__ __forceinline__ float4 scale4(float4 v, float k) {
-  return make_float4(__fmul_rn(v.x, k), __fmul_rn(v.y, k), __fmul_rn(v.z, k), __fmul_rn(v.w, k));
-}
 __device__ __forceinline__ float4 max4(float4 a, float4 b) {
   return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
 }

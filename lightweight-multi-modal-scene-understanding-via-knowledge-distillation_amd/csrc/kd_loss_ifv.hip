@@ -17,7 +17,7 @@
 // thread of the 8-lanes-per-row pass cannot hold NC accumulators per column, so it is a sweep of its own in the class-sum layout.
 // No floating-point atomics, a fixed order everywhere; S and T go
 // through the same instruction sequence: identical bits in both give sS - sT == 0 for every pixel, the value 0 and ds = +-0.
-#include "kd_common.h"
+#include "kd_loss_common.h"
 
 #include <cmath>
 
@@ -69,23 +69,7 @@ inline IfvWs ifv_ws(int B, int HW, int Cs, int Ct, int NC) {
   return w;
 }
 
-// 1 / |x| correctly rounded (sqrt, then a true division); 0 for a norm of at most 1e-12
-__device__ __forceinline__ float inv_norm(float ss) {
-  const float r = __fsqrt_rn(ss);
-  return r > 1e-12f ? __fdiv_rn(1.f, r) : 0.f;
-}
-__device__ __forceinline__ float sumsq4(float4 v, float acc) { return fmaf(v.w, v.w, fmaf(v.z, v.z, fmaf(v.y, v.y, fmaf(v.x, v.x, acc)))); }
 __device__ __forceinline__ float dot4(float4 a, float4 b, float acc) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc)))); }
-__device__ __forceinline__ float4 scale4(float4 v, float k) {
-  return make_float4(__fmul_rn(v.x, k), __fmul_rn(v.y, k), __fmul_rn(v.z, k), __fmul_rn(v.w, k));
-}
-// the sum over the 8 lanes that share a row: a butterfly, so every lane holds the same bits
-__device__ __forceinline__ float row8_sum(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return v;
-}
 // the class of a pixel, or -1 when it is not kept
 __device__ __forceinline__ int kept_class(int64_t y, int ignore_index, int NC) {
   return (y != (int64_t)ignore_index && y >= 0 && y < (int64_t)NC) ? (int)y : -1;

@@ -6,7 +6,7 @@
 // bits, forms g_k, sums e_k g_k and scatters dL/dp_{i,c} into the workspace; one block sums the L_{b,c} in double; a point-wise
 // pass recomputes the softmax, joins a pixel's NC coefficients and stores or adds dzs.
 // No atomics and a fixed order everywhere: the same input gives the same bits on every call and every graph replay.
-#include "kd_common.h"
+#include "kd_loss_common.h"
 
 #include <cmath>
 
@@ -23,16 +23,10 @@ struct LovaszArgs {
   int B, NC, HW, NPAD;
 };
 
-// kd_loss_region.hip's softmax_c at T = 1, operation for operation (the probabilities only)
+// the probabilities of softmax_c at T = 1; the log-probabilities are not used
 __device__ __forceinline__ void softmax_p(const float* z, int NC, float* p) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) mx = fmaxf(mx, z[j] * 1.f);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) { p[j] = expf(z[j] * 1.f - mx); s += p[j]; }
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) p[j] = p[j] / s;
+  float lp[MAXC];
+  softmax_c<MAXC>(z, NC, 1.f, p, lp);
 }
 
 inline int lovasz_npad(int HW) {
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(MAX_T) void lovasz_sort_kernel(LovaszArgs a) {
     unsigned long long key = PAD;
     if (i < a.HW) {
       const int64_t y = y0[i];
-      if (y != a.ignore_index && y >= 0 && y < a.NC) {
+      if (KD_KEPT_LABEL(y, a.ignore_index, a.NC)) {
         float z[MAXC], p[MAXC];
 #pragma unroll
         for (int j = 0; j < MAXC; ++j) if (j < a.NC) z[j] = z0[(int64_t)j * a.HW + i];
@@ -213,7 +207,7 @@ __global__ __launch_bounds__(256) void lovasz_grad_kernel(LovaszGradArgs a) {
     float g[MAXC];
 #pragma unroll
     for (int j = 0; j < MAXC; ++j) g[j] = 0.f;
-    const bool kept = y != a.ignore_index && y >= 0 && y < a.NC;
+    const bool kept = KD_KEPT_LABEL(y, a.ignore_index, a.NC);
     if (kept) {
       float z[MAXC], p[MAXC], q[MAXC], dot = 0.f;
 #pragma unroll

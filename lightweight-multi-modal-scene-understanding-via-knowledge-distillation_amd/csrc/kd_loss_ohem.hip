@@ -16,7 +16,7 @@
 // The bucket choice is folded into the pass that needs it (a block scans at most 2048 counters), which saves three one-block
 // launches.  Histograms are privatised in LDS and flushed with integer atomics; there is no floating-point atomic and no host read:
 // the same input gives the same bytes on every call and every graph replay, and S is a function of the values alone.
-#include "kd_common.h"
+#include "kd_loss_common.h"
 
 #include <cmath>
 #include <cstring>
@@ -40,20 +40,6 @@ struct OhemArgs {
   float* vals; int64_t* counts; float* dzs; float* nll_out; unsigned char* keep_out;
   int64_t npix; int HW; int NC;
 };
-
-// kd_loss.hip's softmax_c, operation for operation
-template <int K>
-__device__ __forceinline__ void softmax_c(const float* z, int NC, float invT, float* p, float* logp) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < K; ++j) if (j < NC) mx = fmaxf(mx, z[j] * invT);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < K; ++j) if (j < NC) { p[j] = expf(z[j] * invT - mx); s += p[j]; }
-  const float ls = logf(s);
-#pragma unroll
-  for (int j = 0; j < K; ++j) if (j < NC) { logp[j] = z[j] * invT - mx - ls; p[j] = p[j] / s; }
-}
 
 __device__ __forceinline__ int kd_wave_sum_int(int v) {
 #pragma unroll
@@ -144,7 +130,7 @@ __global__ __launch_bounds__(256) void ohem_score_kernel(OhemArgs a) {
     for (int j = 0; j < K; ++j) if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw];
     const int64_t y = a.target[i];
     unsigned key = SENT;
-    if (y != a.ignore_index && y >= 0 && y < a.NC) {
+    if (KD_KEPT_LABEL(y, a.ignore_index, a.NC)) {
       softmax_c<K>(z, a.NC, 1.f, p, lp);
       float nll = 0.f;
 #pragma unroll
@@ -353,19 +339,13 @@ int kd_seg_ohem_fwd_bwd(const float* zs, const float* zt, const int64_t* target,
   OhemArgs a{zs, zt, target, class_w, ignore_index, T, alpha, gscale, gscale_dev, lambda_bits, min_kept, min_divisor,
              slab, hist, state, keys, vals, counts_out, dzs, nll_out, keep_out, npix, HW, NC};
   const dim3 g((unsigned)grid), blk(256);
-  if (NC <= 4) hipLaunchKernelGGL(ohem_score_kernel<4>, g, blk, 0, st, a);
-  else if (NC <= 8) hipLaunchKernelGGL(ohem_score_kernel<8>, g, blk, 0, st, a);
-  else hipLaunchKernelGGL(ohem_score_kernel<16>, g, blk, 0, st, a);
+  KD_LAUNCH_CLASS_BUCKET(ohem_score_kernel, NC, g, blk, st, a);
   hipLaunchKernelGGL(ohem_digit_kernel<2>, g, blk, 0, st, a);
   hipLaunchKernelGGL(ohem_digit_kernel<3>, g, blk, 0, st, a);
   hipLaunchKernelGGL(ohem_sum_kernel, g, blk, 0, st, a);
   hipLaunchKernelGGL(ohem_final_kernel, dim3(1), dim3(256), 0, st, (const double*)slab, (int)grid, (double)npix, (const unsigned*)state, vals,
                      counts_out);
-  if (dzs) {
-    if (NC <= 4) hipLaunchKernelGGL(ohem_grad_kernel<4>, g, blk, 0, st, a);
-    else if (NC <= 8) hipLaunchKernelGGL(ohem_grad_kernel<8>, g, blk, 0, st, a);
-    else hipLaunchKernelGGL(ohem_grad_kernel<16>, g, blk, 0, st, a);
-  }
+  if (dzs) KD_LAUNCH_CLASS_BUCKET(ohem_grad_kernel, NC, g, blk, st, a);
   return kd_check_launch("kd_seg_ohem_fwd_bwd");
 }
 

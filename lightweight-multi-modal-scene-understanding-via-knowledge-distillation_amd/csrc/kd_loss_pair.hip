@@ -14,7 +14,7 @@
 // 16-byte stores.
 // No atomics, a fixed order everywhere, and S and T go through the same instruction sequence: with identical bits in both the three
 // Gram matrices are identical bit for bit, the value is exactly 0 and ds is +-0.
-#include "kd_common.h"
+#include "kd_loss_common.h"
 
 #include <cmath>
 
@@ -99,23 +99,6 @@ struct PairArgs {
   float* ds; const float* gdev; float gcoef;
   int HW, Cs, Ct, Csp, Ctp, nsc, ntc, nss, nts, ntiles, slices, slice_rows, resident, cgroups;
 };
-
-// 1 / |x| correctly rounded (sqrt, then a true division); 0 for a row whose norm is at most 1e-12
-__device__ __forceinline__ float inv_norm(float ss) {
-  const float r = __fsqrt_rn(ss);
-  return r > 1e-12f ? __fdiv_rn(1.f, r) : 0.f;
-}
-__device__ __forceinline__ float sumsq4(float4 v, float acc) { return fmaf(v.w, v.w, fmaf(v.z, v.z, fmaf(v.y, v.y, fmaf(v.x, v.x, acc)))); }
-__device__ __forceinline__ float4 scale4(float4 v, float k) {
-  return make_float4(__fmul_rn(v.x, k), __fmul_rn(v.y, k), __fmul_rn(v.z, k), __fmul_rn(v.w, k));
-}
-// the sum over the 8 lanes that share a row: a butterfly, so every lane holds the same bits
-__device__ __forceinline__ float row8_sum(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return v;
-}
 
 // GQ: the float4 columns a thread holds of a row of the Gram chunk (8 threads per row): 4 up to 128 channels, 8 above
 

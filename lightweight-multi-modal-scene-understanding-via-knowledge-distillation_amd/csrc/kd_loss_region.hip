@@ -6,7 +6,7 @@
 // Launch layout (mirrored by tests/_fp64_region_loss_ref.py): 256 threads, at most 1024 blocks, a thread adds its pixels in fp32,
 // a wave its 64 lanes (6 butterfly steps), a block its 4 waves; the slab rows and everything after them are summed in double.
 // No atomics and a fixed order everywhere: the same input gives the same bits on every call and every graph replay.
-#include "kd_common.h"
+#include "kd_loss_common.h"
 
 #include <cmath>
 
@@ -23,19 +23,6 @@ struct RegionArgs {
   float* slab; float* vals; float* dzs;
   int64_t npix; int HW; int NC;
 };
-
-// kd_loss.hip's softmax_c, operation for operation
-__device__ __forceinline__ void softmax_c(const float* z, int NC, float invT, float* p, float* logp) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) mx = fmaxf(mx, z[j] * invT);
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) { p[j] = expf(z[j] * invT - mx); s += p[j]; }
-  const float ls = logf(s);
-#pragma unroll
-  for (int j = 0; j < MAXC; ++j) if (j < NC) { logp[j] = z[j] * invT - mx - ls; p[j] = p[j] / s; }
-}
 
 // om^e for om in [0, 1]: the exponents 0, 1 and 2 (gamma = 2 is the default) without powf
 __device__ __forceinline__ float pow_om(float om, float e) {
@@ -62,8 +49,8 @@ __global__ __launch_bounds__(256) void region_partial_kernel(RegionArgs a) {
 #pragma unroll
     for (int j = 0; j < MAXC; ++j) if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw];
     const int64_t y = a.target[i];
-    if (y != a.ignore_index && y >= 0 && y < a.NC) {
-      softmax_c(z, a.NC, 1.f, p, lp);
+    if (KD_KEPT_LABEL(y, a.ignore_index, a.NC)) {
+      softmax_c<MAXC>(z, a.NC, 1.f, p, lp);
       float py, lpy, om;
       pick(p, lp, a.NC, (int)y, py, lpy, om);
       const float w = a.cw ? a.cw[y] : 1.f;
@@ -79,8 +66,8 @@ __global__ __launch_bounds__(256) void region_partial_kernel(RegionArgs a) {
       float zt[MAXC], pt[MAXC], lpt[MAXC];
 #pragma unroll
       for (int j = 0; j < MAXC; ++j) if (j < a.NC) zt[j] = a.zt[(b * a.NC + j) * a.HW + hw];
-      softmax_c(z, a.NC, 1.f / a.T, p, lp);
-      softmax_c(zt, a.NC, 1.f / a.T, pt, lpt);
+      softmax_c<MAXC>(z, a.NC, 1.f / a.T, p, lp);
+      softmax_c<MAXC>(zt, a.NC, 1.f / a.T, pt, lpt);
 #pragma unroll
       for (int j = 0; j < MAXC; ++j) if (j < a.NC) v[2] += pt[j] > 0.f ? pt[j] * (lpt[j] - lp[j]) : 0.f;
     }
@@ -161,8 +148,8 @@ __global__ __launch_bounds__(256) void region_grad_kernel(RegionArgs a) {
 #pragma unroll
     for (int j = 0; j < MAXC; ++j) { g[j] = 0.f; if (j < a.NC) z[j] = a.zs[(b * a.NC + j) * a.HW + hw]; }
     const int64_t y = a.target[i];
-    if (y != a.ignore_index && y >= 0 && y < a.NC) {
-      softmax_c(z, a.NC, 1.f, p, lp);
+    if (KD_KEPT_LABEL(y, a.ignore_index, a.NC)) {
+      softmax_c<MAXC>(z, a.NC, 1.f, p, lp);
       if (a.wf > 0.f) {
         float py, lpy, om;
         pick(p, lp, a.NC, (int)y, py, lpy, om);
@@ -185,8 +172,8 @@ __global__ __launch_bounds__(256) void region_grad_kernel(RegionArgs a) {
       float zt[MAXC], pt[MAXC], lpt[MAXC];
 #pragma unroll
       for (int j = 0; j < MAXC; ++j) if (j < a.NC) zt[j] = a.zt[(b * a.NC + j) * a.HW + hw];
-      softmax_c(z, a.NC, 1.f / a.T, p, lp);
-      softmax_c(zt, a.NC, 1.f / a.T, pt, lpt);
+      softmax_c<MAXC>(z, a.NC, 1.f / a.T, p, lp);
+      softmax_c<MAXC>(zt, a.NC, 1.f / a.T, pt, lpt);
 #pragma unroll
       for (int j = 0; j < MAXC; ++j) if (j < a.NC) g[j] = fmaf(klc, p[j] - pt[j], g[j]);
     }

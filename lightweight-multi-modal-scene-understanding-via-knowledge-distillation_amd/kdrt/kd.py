@@ -14,7 +14,7 @@ import torch
 from . import gradsink, ops, units
 from .ddp import BucketedAllReduce
 from .lib import KDError
-from .losses import ChannelKD, IntraClassKD, LovaszLoss, OhemCE, PairKD, RegionLoss, kd_objective, kd_objective_backward
+from .losses import check_feature_loss, check_hard_loss, kd_objective, kd_objective_backward
 from .optim import AccumCycle, FusedAdamW
 
 
@@ -31,8 +31,7 @@ class _TakesAccumSteps(type):
     (see ChannelKD, PairKD, IntraClassKD)."""
 
     def __call__(cls, *args, accum_steps=None, feature_loss=None, **kw):
-        if feature_loss is not None and not isinstance(feature_loss, (ChannelKD, PairKD, IntraClassKD)):
-            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD, a kdrt.losses.PairKD, a kdrt.losses.IntraClassKD or None, got {type(feature_loss).__name__}")
+        check_feature_loss(feature_loss)
         step = super().__call__(*args, **kw)
         step.feature_loss = feature_loss
         step.cycle = AccumCycle(step.opt, step.reducer, accum_steps)
@@ -73,9 +72,7 @@ class KDStep(metaclass=_TakesAccumSteps):
         # with equal shards the averaged per-rank gradient is the global batch's.
         # A kdrt.losses.OhemCE averages the weighted CE over the mined pixels only (2 to 16 classes): one kd_seg_ohem_fwd_bwd call in
         # the CE call's place, no host read, so GraphedKDStep replays it unchanged.  Each rank mines its own shard.
-        if hard_loss is not None and not isinstance(hard_loss, (RegionLoss, LovaszLoss, OhemCE)):
-            raise ValueError("hard_loss must be a kdrt.losses.RegionLoss, a kdrt.losses.LovaszLoss, a kdrt.losses.OhemCE or None, "
-                             f"got {type(hard_loss).__name__}")
+        check_hard_loss(hard_loss)
         self.hard_loss = hard_loss
         self.reducer = reducer
         self.sink = gradsink.install(optimizer.flat, reducer)      # backward kernels write into the flat grad buffer

@@ -9,6 +9,7 @@
                   csrc/kd_loss_lovasz.hip on the same stream, adding its value and its gradient to what the base call wrote
   ohem_seg_loss : the opt-in online-hard-example-mining cross-entropy (OhemCE) in place of the weighted CE, 2 to 16 classes: an exact
                   order-statistic selection on the device, then the CE over the kept pixels (csrc/kd_loss_ohem.hip)
+  hard_seg_loss : whichever of the four above the type of its `spec` names (None: seg_loss); what Trainer trains with
   feature_mse   : F.mse_loss forward + gradient
   channel_kd    : the opt-in channel-wise distillation feature term (ChannelKD; Shu et al., ICCV 2021) in the feature MSE's place:
                   a temperature softmax down the H*W positions of every channel of every image, KL to the teacher's
@@ -29,8 +30,8 @@
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
-from typing import Dict, Optional
+from dataclasses import dataclass, field
+from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
@@ -62,53 +63,25 @@ def _check_class_weights(logits, class_w):
                       f"{logits.device}, got {what}")
 
 
-class _SegLossFn(torch.autograd.Function):
-    """forward: loss values only; backward: one more fused call that writes dL/dlogits scaled by the
-    upstream gradient read from device memory (no host sync, no extra elementwise pass)."""
+def _ce_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, losses, dzs):
+    """the default hard-label term (spec None): the weighted CE, losses[0] = CE, [1] = KL, [2] = the sum of the kept weights"""
+    B, NC, H, W = zs.shape
+    nbytes = lib.kd_seg_loss_ws_bytes(B * H * W)
+    ws = ops.workspace(nbytes, zs.device)
+    lib.call("kd_seg_loss_fwd_bwd", P(zs), P(zt), P(target), P(class_w), int(ignore_index), float(T), float(alpha),
+             1.0, P(gdev), P(losses), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
 
-    @staticmethod
-    def _call(zs, zt, target, class_w, ignore_index, T, alpha, gdev, losses, dzs):
-        B, NC, H, W = zs.shape
-        nbytes = lib.kd_seg_loss_ws_bytes(B * H * W)
-        ws = ops.workspace(nbytes, zs.device)
-        lib.call("kd_seg_loss_fwd_bwd", P(zs), P(zt), P(target), P(class_w), int(ignore_index), float(T), float(alpha),
-                 1.0, P(gdev), P(losses), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
 
-    @staticmethod
-    def forward(ctx, zs, zt, target, class_w, ignore_index, T, alpha):
-        ops.require_gpu_tensor(zs, "seg_loss")
-        zs_c = zs.detach().contiguous()
-        zt_c = None if zt is None else zt.detach().contiguous()
-        target = target.contiguous()
-        if target.dtype != torch.int64:
-            raise KDError("segmentation target must be int64")
-        _check_target(zs_c, target)
-        _check_class_weights(zs_c, class_w)
-        losses = torch.empty(4, device=zs.device, dtype=torch.float32)
-        _SegLossFn._call(zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, losses, None)
-        ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha)
-        kl = losses[1]
-        ctx.mark_non_differentiable(kl)
-        return losses[0], kl
-
-    @staticmethod
-    def backward(ctx, g_ce, _g_kl):
-        # the gradient through `ce` is d(CE + alpha*T^2*KL)/dzs (kd_objective adds KL's value separately)
-        zs_c, zt_c, target, class_w, ignore_index, T, alpha = ctx.args
-        losses = torch.empty(4, device=zs_c.device, dtype=torch.float32)
-        dzs = torch.empty_like(zs_c)
-        g = g_ce.contiguous().view(1)
-        _SegLossFn._call(zs_c, zt_c, target, class_w, ignore_index, T, alpha, g, losses, dzs)
-        return dzs, None, None, None, None, None, None
+def _expect_spec(fn, spec, cls):
+    if not isinstance(spec, cls):
+        raise KDError(f"{fn}: spec must be a kdrt.losses.{cls.__name__}, got {type(spec).__name__}")
 
 
 def seg_loss(logits, target, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
              teacher_logits: Optional[torch.Tensor] = None, T: float = 4.0, alpha: float = 1.0):
     """-> (ce, kl).  The gradient that flows back through `ce` is that of ce + alpha*T^2*kl
     (kl is returned for logging / for adding its VALUE to the total)."""
-    if teacher_logits is None:
-        alpha = 0.0
-    return _SegLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T, alpha)
+    return hard_seg_loss(logits, target, None, class_weights, ignore_index, teacher_logits, T, alpha)[:2]
 
 
 @dataclass(frozen=True)
@@ -147,61 +120,15 @@ class RegionLoss:
 
 
 REGION_VALS = 17          # floats kd_seg_region_loss_fwd_bwd writes: L_hard, KL, sum w, Focal, Tversky, TI_c[4], gradient coefficients[8]
-
-
-def _check_region_spec(spec):
-    if not isinstance(spec, RegionLoss):
-        raise KDError(f"the hard-label loss must be a kdrt.losses.RegionLoss (or None for the weighted CE), got {type(spec).__name__}")
-
-
 HARD_MAX_NC = 4           # RegionLoss and LovaszLoss: per-class slots of REGION_VALS / LOVASZ_VALS and of their kernels
-
-
-def _check_hard_classes(name, NC):
-    """the weighted CE + KL runs 2..16 classes; the region and Lovasz kernels keep their limit of 4"""
-    if NC > HARD_MAX_NC:
-        raise KDError(f"{name}: at most {HARD_MAX_NC} classes, the logits have {NC}; 5 to 16 classes train with the weighted CE "
-                      "(hard_loss=None)")
 
 
 def _region_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, vals, dzs):
     B, NC, H, W = zs.shape
-    _check_hard_classes("RegionLoss", NC)
     nbytes = lib.kd_seg_region_loss_ws_bytes(B * H * W)
     ws = ops.workspace(nbytes, zs.device)
     lib.call("kd_seg_region_loss_fwd_bwd", P(zs), P(zt), P(target), P(class_w), int(ignore_index), float(T), float(alpha),
              1.0, P(gdev), *spec.args(), P(vals), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
-
-
-class _RegionLossFn(torch.autograd.Function):
-    """_SegLossFn with the region loss as the hard-label term: forward values only, backward one more fused call."""
-
-    @staticmethod
-    def forward(ctx, zs, zt, target, class_w, ignore_index, T, alpha, spec):
-        ops.require_gpu_tensor(zs, "region_seg_loss")
-        _check_region_spec(spec)
-        zs_c = zs.detach().contiguous()
-        zt_c = None if zt is None else zt.detach().contiguous()
-        target = target.contiguous()
-        if target.dtype != torch.int64:
-            raise KDError("segmentation target must be int64")
-        _check_target(zs_c, target)
-        _check_class_weights(zs_c, class_w)
-        vals = torch.empty(REGION_VALS, device=zs.device, dtype=torch.float32)
-        _region_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, vals, None)
-        ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec)
-        kl, focal, tversky, class_ti = vals[1], vals[3], vals[4], vals[5:5 + zs_c.shape[1]]
-        ctx.mark_non_differentiable(kl, focal, tversky, class_ti)
-        return vals[0], kl, focal, tversky, class_ti
-
-    @staticmethod
-    def backward(ctx, g_hard, *_):
-        # the gradient through `hard` is d(L_hard + alpha*T^2*KL)/dzs (kd_objective adds KL's value separately)
-        zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec = ctx.args
-        vals = torch.empty(REGION_VALS, device=zs_c.device, dtype=torch.float32)
-        dzs = torch.empty_like(zs_c)
-        _region_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, g_hard.contiguous().view(1), vals, dzs)
-        return dzs, None, None, None, None, None, None, None
 
 
 def region_seg_loss(logits, target, spec: RegionLoss, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
@@ -210,10 +137,8 @@ def region_seg_loss(logits, target, spec: RegionLoss, class_weights: Optional[to
     class weights enter the focal term only).  The gradient that flows back through `hard` is that of hard + alpha*T^2*kl.
     parts = {"focal", "tversky", "class_ti"}: device scalars and the [NC] vector of per-class Tversky indices (detached; a term
     whose weight is 0 reads 0)."""
-    if teacher_logits is None:
-        alpha = 0.0
-    hard, kl, focal, tversky, class_ti = _RegionLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T, alpha, spec)
-    return hard, kl, {"focal": focal, "tversky": tversky, "class_ti": class_ti}
+    _expect_spec("region_seg_loss", spec, RegionLoss)
+    return hard_seg_loss(logits, target, spec, class_weights, ignore_index, teacher_logits, T, alpha)
 
 
 @dataclass(frozen=True)
@@ -248,7 +173,6 @@ LOVASZ_MAX_HW = 16384     # 8-byte keys of one image in the LDS of one CU
 def _lovasz_call(spec, zs, target, ignore_index, gdev, vals, hard, dzs):
     """the Lovasz call that follows the base call on the same stream: hard[0] += weight * L, dzs += weight * gdev[0] * dL/dzs"""
     B, NC, H, W = zs.shape
-    _check_hard_classes("LovaszLoss", NC)
     if H * W > LOVASZ_MAX_HW:
         raise KDError(f"LovaszLoss: a {H} x {W} map has {H * W} pixels per image, the per-image sort holds at most {LOVASZ_MAX_HW} (128 x 128)")
     nbytes = lib.kd_seg_lovasz_ws_bytes(B, NC, H * W)
@@ -260,47 +184,9 @@ def _lovasz_call(spec, zs, target, ignore_index, gdev, vals, hard, dzs):
 def _hard_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, lov, dzs):
     """base call (weighted CE or region loss) into hard / dzs, then the Lovasz call adding to both.  hard: REGION_VALS floats
     ([0] the hard-label term, [1] KL in either layout), lov: LOVASZ_VALS floats."""
-    _check_hard_classes("LovaszLoss", zs.shape[1])                # before the base call writes anything
-    if spec.base is None:
-        _SegLossFn._call(zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, dzs)
-    else:
-        _region_call(spec.base, zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, dzs)
-    _lovasz_call(spec, zs, target, ignore_index, gdev, lov, hard, dzs)
-
-
-class _LovaszLossFn(torch.autograd.Function):
-    """_SegLossFn / _RegionLossFn with the Lovasz term added: the two calls of the fused objective, forward values only, backward
-    both again with the gradient."""
-
-    @staticmethod
-    def forward(ctx, zs, zt, target, class_w, ignore_index, T, alpha, spec):
-        ops.require_gpu_tensor(zs, "lovasz_seg_loss")
-        if not isinstance(spec, LovaszLoss):
-            raise KDError(f"lovasz_seg_loss: spec must be a kdrt.losses.LovaszLoss, got {type(spec).__name__}")
-        zs_c = zs.detach().contiguous()
-        zt_c = None if zt is None else zt.detach().contiguous()
-        target = target.contiguous()
-        if target.dtype != torch.int64:
-            raise KDError("segmentation target must be int64")
-        _check_target(zs_c, target)
-        _check_class_weights(zs_c, class_w)
-        hard = torch.zeros(REGION_VALS, device=zs.device, dtype=torch.float32)
-        lov = torch.empty(LOVASZ_VALS, device=zs.device, dtype=torch.float32)
-        _hard_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, hard, lov, None)
-        ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec)
-        kl, focal, tversky, lovasz, class_lovasz = hard[1], hard[3], hard[4], lov[0], lov[1:1 + zs_c.shape[1]]
-        ctx.mark_non_differentiable(kl, focal, tversky, lovasz, class_lovasz)
-        return hard[0], kl, focal, tversky, lovasz, class_lovasz
-
-    @staticmethod
-    def backward(ctx, g_hard, *_):
-        # the gradient through `hard` is d(L_hard + alpha*T^2*KL)/dzs (kd_objective adds KL's value separately)
-        zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec = ctx.args
-        hard = torch.empty(REGION_VALS, device=zs_c.device, dtype=torch.float32)
-        lov = torch.empty(LOVASZ_VALS, device=zs_c.device, dtype=torch.float32)
-        dzs = torch.empty_like(zs_c)
-        _hard_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, g_hard.contiguous().view(1), hard, lov, dzs)
-        return dzs, None, None, None, None, None, None, None
+    base = _ce_call if spec.base is None else _region_call
+    base(spec.base, zs, zt, target, class_w, ignore_index, T, alpha, gdev, hard, dzs)
+    _lovasz_call(spec, zs, target, ignore_index, gdev, lov, hard, dzs)     # looked up here, at call time: tests replace it
 
 
 def lovasz_seg_loss(logits, target, spec: LovaszLoss, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
@@ -310,14 +196,8 @@ def lovasz_seg_loss(logits, target, spec: LovaszLoss, class_weights: Optional[to
     parts = {"lovasz", "class_lovasz"}: the unweighted Lovasz value and the [NC] vector of per-class means of L_{b,c} over the
     images where the class is present (0 if never), detached; with a RegionLoss base also its "focal" and "tversky".
     Data parallel: the Lovasz term is a mean over images, so with equal shards the mean of the per-rank values is the global one."""
-    if teacher_logits is None:
-        alpha = 0.0
-    hard, kl, focal, tversky, lovasz, class_lovasz = _LovaszLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T,
-                                                                         alpha, spec)
-    parts = {"lovasz": lovasz, "class_lovasz": class_lovasz}
-    if spec.base is not None:
-        parts.update(focal=focal, tversky=tversky)
-    return hard, kl, parts
+    _expect_spec("lovasz_seg_loss", spec, LovaszLoss)
+    return hard_seg_loss(logits, target, spec, class_weights, ignore_index, teacher_logits, T, alpha)
 
 
 @dataclass(frozen=True)
@@ -363,14 +243,104 @@ def _ohem_call(spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, vals
              B, NC, H * W, P(ws), nbytes, stream())
 
 
-class _OhemLossFn(torch.autograd.Function):
-    """_SegLossFn with the mined CE as the hard-label term: forward values only, backward one more fused call."""
+def ohem_seg_loss(logits, target, spec: OhemCE, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
+                  teacher_logits: Optional[torch.Tensor] = None, T: float = 4.0, alpha: float = 1.0):
+    """-> (hard, kl, parts): seg_loss with the weighted CE averaged over the mined pixels only (see OhemCE), 2 to 16 classes.  The
+    gradient that flows back through `hard` is that of hard + alpha*T^2*kl, the kept set held constant.
+    parts = {"ce_all", "theta", "kept"}: the weighted CE over every kept-label pixel (for logging), the cut-off on -log p_y and the
+    kept share |S| / n, device scalars, detached.  Data parallel: each rank mines its own shard."""
+    _expect_spec("ohem_seg_loss", spec, OhemCE)
+    hard, kl, parts = hard_seg_loss(logits, target, spec, class_weights, ignore_index, teacher_logits, T, alpha)
+    return hard, kl, {k.removeprefix("ohem_"): v for k, v in parts.items()}      # the objective's "ohem_theta", "ohem_kept"
+
+
+# ---------------------------------------------------------------------------------------------
+# The hard-label terms, one row each.  The rows are all that seg_loss .. ohem_seg_loss, kd_objective and kd_objective_backward know of
+# a term; a new term supplies a spec class, its call and a row.
+_FUNCTION, _AUTOGRAD, _FUSED = _FORMS = ("function", "autograd", "fused")    # a term's own *_seg_loss function, kd_objective, kd_objective_backward
+
+
+@dataclass(frozen=True)
+class _Part:
+    """where a named part lives in the value buffers of its term"""
+    at: int
+    buf: int = 0
+    per_class: bool = False                       # the [NC] vector that starts at `at`, not the scalar there
+    forms: Tuple[str, ...] = _FORMS               # the forms that report it
+
+
+@dataclass(frozen=True, eq=False)
+class _HardTerm:
+    """one hard-label term: its launches, its value buffers, its class limit and where its named parts lie"""
+    fn: str                                       # the term's public function, for messages
+    call: Callable                                # (spec, zs, zt, target, class_w, ignore_index, T, alpha, gdev, *bufs, dzs): the launches
+    sizes: Tuple[int, ...]                        # floats per value buffer; bufs[0][0] is the term's value, bufs[0][1] the KL
+    zeroed: bool = False                          # whether bufs[0] must start zeroed
+    max_nc: Optional[int] = None                  # class limit, checked before the first launch; None: the kernel's own 2..16
+    parts: Dict[str, _Part] = field(default_factory=dict)
+    absent: Callable = lambda spec: ()            # the parts that this spec does not report
+
+    def check_classes(self, spec, NC):
+        if self.max_nc is not None and NC > self.max_nc:
+            raise KDError(f"{type(spec).__name__}: at most {self.max_nc} classes, got {NC}; 5 to 16 classes train with the weighted CE "
+                          "(hard_loss=None) or an OhemCE")
+
+    def alloc(self, dev, scratch=False):
+        """the value buffers; scratch: for a call whose values nobody reads (the autograd backward), never zeroed"""
+        first = torch.zeros if self.zeroed and not scratch else torch.empty
+        return tuple((torch.empty if i else first)(n, device=dev, dtype=torch.float32) for i, n in enumerate(self.sizes))
+
+    def names(self, spec, form):
+        skip = self.absent(spec)
+        return [k for k, p in self.parts.items() if form in p.forms and k not in skip]
+
+    def read(self, spec, form, bufs, NC):
+        """-> {name: view of its buffer} of the parts that `form` reports"""
+        at = ((k, self.parts[k]) for k in self.names(spec, form))
+        return {k: bufs[p.buf][p.at:p.at + NC] if p.per_class else bufs[p.buf][p.at] for k, p in at}
+
+
+_HARD_TERMS = {
+    type(None): _HardTerm("seg_loss", _ce_call, (4,)),
+    RegionLoss: _HardTerm("region_seg_loss", _region_call, (REGION_VALS,), max_nc=HARD_MAX_NC, parts={
+        "focal": _Part(3), "tversky": _Part(4), "class_ti": _Part(5, per_class=True, forms=(_FUNCTION,))}),
+    LovaszLoss: _HardTerm("lovasz_seg_loss", _hard_call, (REGION_VALS, LOVASZ_VALS), zeroed=True, max_nc=HARD_MAX_NC, parts={
+        "lovasz": _Part(0, buf=1), "class_lovasz": _Part(1, buf=1, per_class=True, forms=(_FUNCTION, _AUTOGRAD)),
+        "focal": _Part(3), "tversky": _Part(4)}, absent=lambda spec: ("focal", "tversky") if spec.base is None else ()),
+    OhemCE: _HardTerm("ohem_seg_loss", _ohem_call, (OHEM_VALS,), parts={
+        "ce_all": _Part(3), "ohem_theta": _Part(4), "ohem_kept": _Part(5)}),
+}
+HARD_LOSSES = tuple(c for c in _HARD_TERMS if c is not type(None))
+
+
+def _term(table, what, spec, error=ValueError):
+    """the row of `spec` in a table of terms; `error` naming every accepted class when it has none (the constructors that take the
+    option raise ValueError, the objective KDError, as they always have)"""
+    for cls, term in table.items():
+        if isinstance(spec, cls):
+            return term
+    accepted = ", ".join(f"a kdrt.losses.{c.__name__}" for c in table if c is not type(None))
+    raise error(f"{what} must be {accepted} or None, got {type(spec).__name__}")
+
+
+def check_hard_loss(spec):
+    """ValueError unless spec is None (the weighted CE) or one of HARD_LOSSES"""
+    _term(_HARD_TERMS, "hard_loss", spec)
+
+
+def check_hard_classes(spec, num_classes):
+    """KDError when the hard-label term of `spec` does not hold `num_classes` classes (RegionLoss and LovaszLoss: at most 4)"""
+    _term(_HARD_TERMS, "hard_loss", spec).check_classes(spec, num_classes)
+
+
+class _HardLossFn(torch.autograd.Function):
+    """The hard-label term of one row (+ alpha*T^2*KL to a teacher's logits).  forward: the loss values only; backward: the row's call
+    once more, which now writes dL/dlogits scaled by the upstream gradient read from device memory (no host sync, no extra
+    elementwise pass)."""
 
     @staticmethod
-    def forward(ctx, zs, zt, target, class_w, ignore_index, T, alpha, spec):
-        ops.require_gpu_tensor(zs, "ohem_seg_loss")
-        if not isinstance(spec, OhemCE):
-            raise KDError(f"ohem_seg_loss: spec must be a kdrt.losses.OhemCE, got {type(spec).__name__}")
+    def forward(ctx, term, spec, zs, zt, target, class_w, ignore_index, T, alpha):
+        ops.require_gpu_tensor(zs, term.fn)
         zs_c = zs.detach().contiguous()
         zt_c = None if zt is None else zt.detach().contiguous()
         target = target.contiguous()
@@ -378,33 +348,41 @@ class _OhemLossFn(torch.autograd.Function):
             raise KDError("segmentation target must be int64")
         _check_target(zs_c, target)
         _check_class_weights(zs_c, class_w)
-        vals = torch.empty(OHEM_VALS, device=zs.device, dtype=torch.float32)
-        _ohem_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, vals, None)
-        ctx.args = (zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec)
-        kl, ce_all, theta, kept = vals[1], vals[3], vals[4], vals[5]
-        ctx.mark_non_differentiable(kl, ce_all, theta, kept)
-        return vals[0], kl, ce_all, theta, kept
+        term.check_classes(spec, zs_c.shape[1])
+        bufs = term.alloc(zs.device)
+        term.call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, None, *bufs, None)
+        ctx.args = (term, spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha)
+        kl = bufs[0][1]
+        parts = term.read(spec, _FUNCTION, bufs, zs_c.shape[1]).values()
+        ctx.mark_non_differentiable(kl, *parts)
+        return (bufs[0][0], kl, *parts)
 
     @staticmethod
     def backward(ctx, g_hard, *_):
         # the gradient through `hard` is d(L_hard + alpha*T^2*KL)/dzs (kd_objective adds KL's value separately)
-        zs_c, zt_c, target, class_w, ignore_index, T, alpha, spec = ctx.args
-        vals = torch.empty(OHEM_VALS, device=zs_c.device, dtype=torch.float32)
+        term, spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha = ctx.args
+        bufs = term.alloc(zs_c.device, scratch=True)
         dzs = torch.empty_like(zs_c)
-        _ohem_call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, g_hard.contiguous().view(1), vals, dzs)
-        return dzs, None, None, None, None, None, None, None
+        term.call(spec, zs_c, zt_c, target, class_w, ignore_index, T, alpha, g_hard.contiguous().view(1), *bufs, dzs)
+        return (None, None, dzs) + (None,) * 6
 
 
-def ohem_seg_loss(logits, target, spec: OhemCE, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
-                  teacher_logits: Optional[torch.Tensor] = None, T: float = 4.0, alpha: float = 1.0):
-    """-> (hard, kl, parts): seg_loss with the weighted CE averaged over the mined pixels only (see OhemCE), 2 to 16 classes.  The
-    gradient that flows back through `hard` is that of hard + alpha*T^2*kl, the kept set held constant.
-    parts = {"ce_all", "theta", "kept"}: the weighted CE over every kept-label pixel (for logging), the cut-off on -log p_y and the
-    kept share |S| / n, device scalars, detached.  Data parallel: each rank mines its own shard."""
+def _hard_seg_loss(term, form, logits, target, spec, class_weights, ignore_index, teacher_logits, T, alpha):
+    """-> (hard, kl, the parts that `form` reports) through the row `term` of `spec`"""
     if teacher_logits is None:
         alpha = 0.0
-    hard, kl, ce_all, theta, kept = _OhemLossFn.apply(logits, teacher_logits, target, class_weights, ignore_index, T, alpha, spec)
-    return hard, kl, {"ce_all": ce_all, "theta": theta, "kept": kept}
+    hard, kl, *vals = _HardLossFn.apply(term, spec, logits, teacher_logits, target, class_weights, ignore_index, T, alpha)
+    parts = dict(zip(term.names(spec, _FUNCTION), vals))
+    return hard, kl, {k: parts[k] for k in term.names(spec, form)}
+
+
+def hard_seg_loss(logits, target, spec=None, class_weights: Optional[torch.Tensor] = None, ignore_index: int = -1,
+                  teacher_logits: Optional[torch.Tensor] = None, T: float = 4.0, alpha: float = 1.0):
+    """-> (hard, kl, parts) for any hard-label spec (None: the weighted CE, no parts): what seg_loss, region_seg_loss, lovasz_seg_loss
+    and ohem_seg_loss return (the OhemCE parts under their names in the objective), chosen by the type of `spec`; ValueError for any
+    other.  The gradient that flows back through `hard` is that of hard + alpha*T^2*kl."""
+    term = _term(_HARD_TERMS, "hard_loss", spec)
+    return _hard_seg_loss(term, _FUNCTION, logits, target, spec, class_weights, ignore_index, teacher_logits, T, alpha)
 
 
 class _MSEFn(torch.autograd.Function):
@@ -517,12 +495,6 @@ IFV_MIN_C, IFV_MAX_C = 4, 256     # csrc/kd_loss_ifv.hip: widths in multiples of
 IFV_MIN_NC, IFV_MAX_NC = 2, 16
 
 
-def _check_feature_spec(spec):
-    if not isinstance(spec, (ChannelKD, PairKD, IntraClassKD)):
-        raise KDError("the feature loss must be a kdrt.losses.ChannelKD, kdrt.losses.PairKD or kdrt.losses.IntraClassKD (or None for "
-                      f"the feature MSE), got {type(spec).__name__}")
-
-
 def _check_cwd_pair(a, b):
     """the kernel indexes both maps as [B*H*W, C] of the student's shape"""
     if a.dim() != 4 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
@@ -535,45 +507,27 @@ def _check_cwd_pair(a, b):
         raise KDError(f"channel_kd: fp32 maps expected, got {a.dtype} and {b.dtype}")
 
 
-def _cwd_call(am, bm, geom, tau, gcoef, gdev, val, ds):
-    """one kd_feat_cwd_fwd_bwd call on the NHWC matrices am, bm [B*H*W, C]: val[0] = CWD, ds = gcoef * gdev[0] * (phi(s) - phi(t))"""
+# The three calls below share one signature, (spec, am, bm, geom, target, NC, ignore_index, gcoef, gdev, val, ds), on the NHWC matrices
+# am [B*H*W, Cs] and bm [B*H*W, Ct] of a map pair: val[0] = the term, ds = gcoef * gdev[0] * (the term's gradient over its own gcoef).
+def _cwd_call(spec, am, bm, geom, target, NC, ignore_index, gcoef, gdev, val, ds):
+    """one kd_feat_cwd_fwd_bwd call: val[0] = CWD, ds = gcoef * gdev[0] * (phi(s) - phi(t))"""
     B, H, W = geom
     C = am.shape[1]
     nbytes = lib.kd_feat_cwd_ws_bytes(B, H * W, C)
     ws = ops.workspace(nbytes, am.device)
-    lib.call("kd_feat_cwd_fwd_bwd", P(am), P(bm), B, H * W, C, float(tau), float(gcoef), P(gdev), P(val), P(ds), None, P(ws), nbytes, stream())
+    lib.call("kd_feat_cwd_fwd_bwd", P(am), P(bm), B, H * W, C, float(spec.tau), float(gcoef), P(gdev), P(val), P(ds), None, P(ws), nbytes,
+             stream())
 
 
-class _ChannelKDFn(torch.autograd.Function):
-    """_MSEFn's shape: forward the value only; backward one more call with the upstream gradient read from device memory, so the
-    gradient coefficient is k = fl32(fl32(tau / (B*C)) * g) -- with g = fl32(beta) from the objective's autograd graph the product
-    kd_objective_backward folds into gcoef on the host."""
-
-    @staticmethod
-    def forward(ctx, a, b, tau):
-        _check_cwd_pair(a, b)
-        ops.require_gpu_tensor(a, "channel_kd")
-        am, geom = ops.nhwc_view(a.detach())
-        bm, _ = ops.nhwc_view(b.detach())
-        val = torch.empty(1, device=a.device, dtype=torch.float32)
-        _cwd_call(am, bm, geom, tau, 0.0, None, val, None)
-        ctx.am, ctx.bm, ctx.geom, ctx.tau = am, bm, geom, tau
-        return val[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        am, bm, geom, tau = ctx.am, ctx.bm, ctx.geom, ctx.tau
-        ds = torch.empty_like(am)
-        val = torch.empty(1, device=am.device, dtype=torch.float32)
-        _cwd_call(am, bm, geom, tau, tau / (geom[0] * am.shape[1]), g.contiguous().view(1), val, ds)
-        return ops.nchw_from_matrix(ds, geom), None, None
+def _cwd_gcoef(spec, geom, am):
+    """tau / (B*C), the host's double rounded to fp32 by the call"""
+    return spec.tau / (geom[0] * am.shape[1])
 
 
 def channel_kd(student_feat, teacher_feat, tau: float = 4.0):
     """CWD(student_feat, teacher_feat; tau) of two [B, C, H, W] fp32 maps (see ChannelKD): a device scalar whose gradient flows to
     the student map only.  KDError on a shape or device mismatch and on a channel count that is no multiple of 4 or above 512."""
-    tau = ChannelKD(tau).tau
-    return _ChannelKDFn.apply(student_feat, teacher_feat, float(tau))
+    return _FEATURE_TERMS[ChannelKD].value(ChannelKD(tau), student_feat, teacher_feat, None, None, None)
 
 
 def _check_pair_pair(a, b):
@@ -591,9 +545,8 @@ def _check_pair_pair(a, b):
         raise KDError(f"pair_kd: fp32 maps expected, got {a.dtype} and {b.dtype}")
 
 
-def _pair_call(am, bm, geom, gcoef, gdev, val, ds):
-    """one kd_feat_pair_fwd_bwd call on the NHWC matrices am [B*H*W, Cs], bm [B*H*W, Ct]: val[0] = PAIR, ds = gcoef * gdev[0] * (B n^2 / 4)
-    * dPAIR/dS"""
+def _pair_call(spec, am, bm, geom, target, NC, ignore_index, gcoef, gdev, val, ds):
+    """one kd_feat_pair_fwd_bwd call: val[0] = PAIR, ds = gcoef * gdev[0] * (B n^2 / 4) * dPAIR/dS"""
     B, H, W = geom
     Cs, Ct = am.shape[1], bm.shape[1]
     nbytes = lib.kd_feat_pair_ws_bytes(B, H * W, Cs, Ct)
@@ -601,41 +554,17 @@ def _pair_call(am, bm, geom, gcoef, gdev, val, ds):
     lib.call("kd_feat_pair_fwd_bwd", P(am), P(bm), B, H * W, Cs, Ct, float(gcoef), P(gdev), P(val), P(ds), None, P(ws), nbytes, stream())
 
 
-def _pair_gcoef(geom):
+def _pair_gcoef(spec, geom, am):
     """4 / (B n^2), the host's double rounded to fp32 by the call"""
     B, H, W = geom
     return 4.0 / (float(B) * float(H * W) * float(H * W))
-
-
-class _PairKDFn(torch.autograd.Function):
-    """_ChannelKDFn's shape: forward the value only; backward one more call with the upstream gradient read from device memory, so the
-    gradient coefficient is k = fl32(fl32(4 / (B n^2)) * g) -- with g = fl32(beta) from the objective's autograd graph the product
-    kd_objective_backward folds into gcoef on the host."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        _check_pair_pair(a, b)
-        am, geom = ops.nhwc_view(a.detach())
-        bm, _ = ops.nhwc_view(b.detach())
-        val = torch.empty(1, device=a.device, dtype=torch.float32)
-        _pair_call(am, bm, geom, 0.0, None, val, None)
-        ctx.am, ctx.bm, ctx.geom = am, bm, geom
-        return val[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        am, bm, geom = ctx.am, ctx.bm, ctx.geom
-        ds = torch.empty_like(am)
-        val = torch.empty(1, device=am.device, dtype=torch.float32)
-        _pair_call(am, bm, geom, _pair_gcoef(geom), g.contiguous().view(1), val, ds)
-        return ops.nchw_from_matrix(ds, geom), None
 
 
 def pair_kd(student_feat, teacher_feat):
     """PAIR(student_feat, teacher_feat) of two fp32 maps [B, Cs, H, W] and [B, Ct, H, W] (see PairKD): a device scalar whose gradient
     flows to the student map only.  KDError on CPU tensors, a dtype other than fp32, differing B, H, W or devices, and on a width that is
     no multiple of 4 or outside 4..256."""
-    return _PairKDFn.apply(student_feat, teacher_feat)
+    return _FEATURE_TERMS[PairKD].value(PairKD(), student_feat, teacher_feat, None, None, None)
 
 
 def _check_ifv_args(a, b, target, num_classes):
@@ -661,9 +590,8 @@ def _check_ifv_args(a, b, target, num_classes):
         raise KDError(f"intra_class_kd: {num_classes} classes unsupported ({IFV_MIN_NC} to {IFV_MAX_NC})")
 
 
-def _ifv_call(am, bm, target, geom, NC, ignore_index, gcoef, gdev, val, ds):
-    """one kd_feat_ifv_fwd_bwd call on the NHWC matrices am [B*H*W, Cs], bm [B*H*W, Ct] and the labels [B, H, W]: val[0] = IFV,
-    ds = gcoef * gdev[0] * (B / 2) * dIFV/dS"""
+def _ifv_call(spec, am, bm, geom, target, NC, ignore_index, gcoef, gdev, val, ds):
+    """one kd_feat_ifv_fwd_bwd call under the labels [B, H, W]: val[0] = IFV, ds = gcoef * gdev[0] * (B / 2) * dIFV/dS"""
     B, H, W = geom
     Cs, Ct = am.shape[1], bm.shape[1]
     nbytes = lib.kd_feat_ifv_ws_bytes(B, H * W, Cs, Ct, NC)
@@ -672,34 +600,9 @@ def _ifv_call(am, bm, target, geom, NC, ignore_index, gcoef, gdev, val, ds):
              None, P(ws), nbytes, stream())
 
 
-def _ifv_gcoef(geom):
+def _ifv_gcoef(spec, geom, am):
     """2 / B, the host's double rounded to fp32 by the call"""
     return 2.0 / float(geom[0])
-
-
-class _IntraClassKDFn(torch.autograd.Function):
-    """_PairKDFn's shape: forward the value only; backward one more call with the upstream gradient read from device memory, so the
-    gradient coefficient is k = fl32(fl32(2 / B) * g) -- with g = fl32(beta) from the objective's autograd graph the product
-    kd_objective_backward folds into gcoef on the host."""
-
-    @staticmethod
-    def forward(ctx, a, b, target, NC, ignore_index):
-        _check_ifv_args(a, b, target, NC)
-        am, geom = ops.nhwc_view(a.detach())
-        bm, _ = ops.nhwc_view(b.detach())
-        target = target.contiguous()
-        val = torch.empty(1, device=a.device, dtype=torch.float32)
-        _ifv_call(am, bm, target, geom, NC, ignore_index, 0.0, None, val, None)
-        ctx.am, ctx.bm, ctx.target, ctx.geom, ctx.NC, ctx.ignore_index = am, bm, target, geom, NC, ignore_index
-        return val[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        am, bm, geom = ctx.am, ctx.bm, ctx.geom
-        ds = torch.empty_like(am)
-        val = torch.empty(1, device=am.device, dtype=torch.float32)
-        _ifv_call(am, bm, ctx.target, geom, ctx.NC, ctx.ignore_index, _ifv_gcoef(geom), g.contiguous().view(1), val, ds)
-        return ops.nchw_from_matrix(ds, geom), None, None, None, None
 
 
 def intra_class_kd(student_feat, teacher_feat, target, num_classes, ignore_index=-1):
@@ -707,7 +610,96 @@ def intra_class_kd(student_feat, teacher_feat, target, num_classes, ignore_index
     `num_classes` classes (see IntraClassKD): a device scalar whose gradient flows to the student map only.  KDError, before any
     launch, on CPU tensors, a dtype other than fp32 / int64, differing B, H, W or devices (a label map of another size included), a
     width that is no multiple of 4 or outside 4..256, and a class count outside 2..16."""
-    return _IntraClassKDFn.apply(student_feat, teacher_feat, target, int(num_classes), int(ignore_index))
+    return _FEATURE_TERMS[IntraClassKD].value(IntraClassKD(), student_feat, teacher_feat, target, int(num_classes), int(ignore_index))
+
+
+# ---------------------------------------------------------------------------------------------
+# The feature terms, one row each: all that channel_kd .. intra_class_kd, kd_objective and kd_objective_backward know of a term.  A new
+# term supplies a spec class, a check of a map pair, a call of the signature above, its host-side gradient coefficient and a row.
+class _FeatureTerm:
+    """one feature term: its check, its call, its gradient coefficient, its part names and how the fused form finishes"""
+
+    def __init__(self, fn, parts, check=lambda a, b, target, NC: None, call=None, gcoef=None):
+        self.fn = fn              # the term's public function, for messages
+        self.parts = parts        # the names of the camera map's and the LiDAR map's value in the objective's parts
+        self.check = check        # (a, b, target, NC): KDError for a map pair (or labels) the kernel cannot take; no launch
+        self.call = call
+        self.gcoef = gcoef        # (spec, geom, am) -> the coefficient of the term's gradient, a Python float
+
+    def value(self, spec, a, b, target, NC, ignore_index):
+        """the autograd form: a device scalar whose gradient flows to the student map `a`"""
+        return _FeatureFn.apply(self, spec, a, b, target, NC, ignore_index)
+
+    def fused_map(self, spec, am, bm, geom, target, NC, ignore_index, beta, out, i, da):
+        """the fused form, map i: ONE call that writes the value to out[i] and the gradient beta * d term / d am to da"""
+        gcoef = float(np.float32(self.gcoef(spec, geom, am)) * np.float32(beta))      # the product the autograd form's backward forms
+        self.call(spec, am, bm, geom, target, NC, ignore_index, gcoef, None, out[i:i + 1], da)
+
+    def fused_total(self, hard, out, maps, ckl, beta):
+        """the fused form's last launch: out[2] = hard[0] + ckl * hard[1] + beta * (out[0] + out[1])"""
+        lib.call("kd_kd_total", P(hard), P(out[0:1]), P(out[1:2]), ckl, beta, P(out[2:3]), stream())
+
+
+class _MSETerm(_FeatureTerm):
+    """The default, the feature MSE: the fused form leaves per-block sums per map and kd_kd_objective_final finishes the two values
+    together with the total."""
+
+    def value(self, spec, a, b, target, NC, ignore_index):
+        return _MSEFn.apply(a, b)
+
+    def fused_map(self, spec, am, bm, geom, target, NC, ignore_index, beta, out, i, da):
+        n = am.numel()
+        slab = torch.empty(lib.kd_mse_slab_blocks(n), device=am.device, dtype=torch.float32)
+        gcoef = float(np.float32(2.0 / n) * np.float32(beta))      # the product autograd's fp32 chain rule forms
+        lib.call("kd_mse_partial", P(am), P(bm), n, gcoef, P(da), P(slab), stream())
+        return slab, n
+
+    def fused_total(self, hard, out, maps, ckl, beta):
+        (slab_c, n_c), (slab_l, n_l) = maps
+        lib.call("kd_kd_objective_final", P(hard), P(slab_c), n_c, P(slab_l), n_l, ckl, beta, P(out), stream())
+
+
+_FEATURE_TERMS = {
+    type(None): _MSETerm("feature_mse", ("mse_cam", "mse_lidar")),
+    ChannelKD: _FeatureTerm("channel_kd", ("cwd_cam", "cwd_lidar"), lambda a, b, target, NC: _check_cwd_pair(a, b), _cwd_call, _cwd_gcoef),
+    PairKD: _FeatureTerm("pair_kd", ("pair_cam", "pair_lidar"), lambda a, b, target, NC: _check_pair_pair(a, b), _pair_call, _pair_gcoef),
+    IntraClassKD: _FeatureTerm("intra_class_kd", ("ifv_cam", "ifv_lidar"), _check_ifv_args, _ifv_call, _ifv_gcoef),
+}
+FEATURE_LOSSES = tuple(c for c in _FEATURE_TERMS if c is not type(None))
+
+
+def check_feature_loss(spec):
+    """ValueError unless spec is None (the feature MSE) or one of FEATURE_LOSSES"""
+    _term(_FEATURE_TERMS, "feature_loss", spec)
+
+
+class _FeatureFn(torch.autograd.Function):
+    """The feature term of one row, in _MSEFn's shape: forward the value only; backward one more call with the upstream gradient read
+    from device memory, so the gradient coefficient is k = fl32(fl32(gcoef) * g) -- with g = fl32(beta) from the objective's autograd
+    graph the product kd_objective_backward folds into gcoef on the host."""
+
+    @staticmethod
+    def forward(ctx, term, spec, a, b, target, NC, ignore_index):
+        term.check(a, b, target, NC)
+        ops.require_gpu_tensor(a, term.fn)
+        am, geom = ops.nhwc_view(a.detach())
+        bm, _ = ops.nhwc_view(b.detach())
+        if target is not None:
+            target = target.contiguous()
+        val = torch.empty(1, device=a.device, dtype=torch.float32)
+        term.call(spec, am, bm, geom, target, NC, ignore_index, 0.0, None, val, None)
+        ctx.args = (term, spec, am, bm, geom, target, NC, ignore_index)
+        return val[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        term, spec, am, bm, geom, target, NC, ignore_index = ctx.args
+        ds = torch.empty_like(am)
+        val = torch.empty(1, device=am.device, dtype=torch.float32)
+        term.call(spec, am, bm, geom, target, NC, ignore_index, term.gcoef(spec, geom, am), g.contiguous().view(1), val, ds)
+        return None, None, ops.nchw_from_matrix(ds, geom), None, None, None, None
+
+_KD_MAPS = ("camera_feat", "lidar_feat")          # the two feature maps of the objective, in the order of a feature term's part names
 
 
 def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
@@ -727,42 +719,17 @@ def kd_objective(student_logits, student_mids: Dict[str, torch.Tensor], teacher_
     feature_loss (an IntraClassKD): beta * (IFV(camera_feat) + IFV(lidar_feat)) under `target` with the logits' class count takes the
     two MSEs' place and parts carries "ifv_cam" / "ifv_lidar".  The label map must have the feature maps' H x W.  A mean over images
     as well.  beta needs re-tuning (see IntraClassKD)."""
-    extra = {}
-    if feature_loss is not None:
-        _check_feature_spec(feature_loss)
-        if isinstance(feature_loss, IntraClassKD):                # before any launch
-            for key in ("camera_feat", "lidar_feat"):
-                _check_ifv_args(student_mids[key], teacher_mids[key], target, student_logits.shape[1])
-    if hard_loss is None:
-        ce, kl = seg_loss(student_logits, target, class_weights, ignore_index, teacher_logits, T, alpha)
-    elif isinstance(hard_loss, OhemCE):
-        ce, kl, op = ohem_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
-        extra = {"ce_all": op["ce_all"], "ohem_theta": op["theta"], "ohem_kept": op["kept"]}
-    elif isinstance(hard_loss, LovaszLoss):
-        ce, kl, extra = lovasz_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
-    else:
-        ce, kl, rp = region_seg_loss(student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
-        extra = {"focal": rp["focal"], "tversky": rp["tversky"]}
-    if feature_loss is None:
-        names = ("mse_cam", "mse_lidar")
-        mse_c = feature_mse(student_mids["camera_feat"], teacher_mids["camera_feat"])
-        mse_l = feature_mse(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
-    elif isinstance(feature_loss, PairKD):
-        names = ("pair_cam", "pair_lidar")
-        mse_c = pair_kd(student_mids["camera_feat"], teacher_mids["camera_feat"])
-        mse_l = pair_kd(student_mids["lidar_feat"], teacher_mids["lidar_feat"])
-    elif isinstance(feature_loss, IntraClassKD):
-        names = ("ifv_cam", "ifv_lidar")
-        NC = student_logits.shape[1]
-        mse_c = intra_class_kd(student_mids["camera_feat"], teacher_mids["camera_feat"], target, NC, ignore_index)
-        mse_l = intra_class_kd(student_mids["lidar_feat"], teacher_mids["lidar_feat"], target, NC, ignore_index)
-    else:
-        names = ("cwd_cam", "cwd_lidar")
-        mse_c = channel_kd(student_mids["camera_feat"], teacher_mids["camera_feat"], feature_loss.tau)
-        mse_l = channel_kd(student_mids["lidar_feat"], teacher_mids["lidar_feat"], feature_loss.tau)
+    feat = _term(_FEATURE_TERMS, "feature_loss", feature_loss, KDError)
+    hard_term = _term(_HARD_TERMS, "hard_loss", hard_loss, KDError)
+    NC = student_logits.shape[1]
+    maps = [(student_mids[key], teacher_mids[key]) for key in _KD_MAPS]
+    for a, b in maps:                                             # before any launch
+        feat.check(a, b, target, NC)
+    ce, kl, extra = _hard_seg_loss(hard_term, _AUTOGRAD, student_logits, target, hard_loss, class_weights, ignore_index, teacher_logits, T, alpha)
+    f_c, f_l = (feat.value(feature_loss, a, b, target, NC, ignore_index) for a, b in maps)
     # `ce` carries the CE+KL gradient; add KL's value without a second gradient path
-    total = ce + (alpha * T * T) * kl.detach() + beta * (mse_c + mse_l)
-    return total, {"ce": ce.detach(), "kl": kl.detach(), names[0]: mse_c.detach(), names[1]: mse_l.detach(), **extra}
+    total = ce + (alpha * T * T) * kl.detach() + beta * (f_c + f_l)
+    return total, {"ce": ce.detach(), "kl": kl.detach(), feat.parts[0]: f_c.detach(), feat.parts[1]: f_l.detach(), **extra}
 
 
 def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor], teacher_logits, teacher_mids, target,
@@ -791,6 +758,8 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
     ops.require_gpu_tensor(zs, "kd_objective_backward")
     if not zs.requires_grad:
         raise KDError("kd_objective_backward: the student logits carry no autograd graph (was the forward run under no_grad?)")
+    hard_term = _term(_HARD_TERMS, "hard_loss", hard_loss, KDError)
+    feat = _term(_FEATURE_TERMS, "feature_loss", feature_loss, KDError)
     dev = zs.device
     zs_c = zs.detach().contiguous()
     zt_c = teacher_logits.detach().contiguous()
@@ -799,96 +768,34 @@ def kd_objective_backward(student_logits, student_mids: Dict[str, torch.Tensor],
         raise KDError("segmentation target must be int64")
     _check_target(zs_c, target)
     _check_class_weights(zs_c, class_weights)
-    B, NC, H, W = zs_c.shape
-    if feature_loss is not None:
-        _check_feature_spec(feature_loss)
-        if isinstance(feature_loss, IntraClassKD):                # before any launch
-            for key in ("camera_feat", "lidar_feat"):
-                _check_ifv_args(student_mids[key], teacher_mids[key], target, NC)
-    vals = torch.empty(8, device=dev, dtype=torch.float32)        # [0:4] seg-loss values, [4] mse_cam, [5] mse_lidar, [6] total
+    NC = zs_c.shape[1]
+    hard_term.check_classes(hard_loss, NC)
+    maps = [(student_mids[key], teacher_mids[key]) for key in _KD_MAPS]
+    for a, b in maps:                                             # before any launch
+        feat.check(a, b, target, NC)
+    bufs = hard_term.alloc(dev)
+    hard = bufs[0]                                                # [0] the hard-label term, [1] KL: what the final kernel reads
     dzs = torch.empty_like(zs_c)
-    nbytes = lib.kd_seg_loss_ws_bytes(B * H * W)
-    ws = ops.workspace(nbytes, dev)
-    hard = vals                                                   # [0] the hard-label term, [1] KL: what the final kernel reads
-    extra = {}
-    if hard_loss is None:
-        lib.call("kd_seg_loss_fwd_bwd", P(zs_c), P(zt_c), P(target), P(class_weights), int(ignore_index), float(T), float(alpha),
-                 1.0, None, P(vals), P(dzs), B, NC, H * W, P(ws), nbytes, stream())
-    elif isinstance(hard_loss, OhemCE):
-        hard = torch.empty(OHEM_VALS, device=dev, dtype=torch.float32)
-        _ohem_call(hard_loss, zs_c, zt_c, target, class_weights, ignore_index, T, alpha, None, hard, dzs)
-        extra = {"ce_all": hard[3], "ohem_theta": hard[4], "ohem_kept": hard[5]}
-    elif isinstance(hard_loss, LovaszLoss):
-        hard = torch.zeros(REGION_VALS, device=dev, dtype=torch.float32)
-        lov = torch.empty(LOVASZ_VALS, device=dev, dtype=torch.float32)
-        _hard_call(hard_loss, zs_c, zt_c, target, class_weights, ignore_index, T, alpha, None, hard, lov, dzs)
-        extra = {"lovasz": lov[0]}
-        if hard_loss.base is not None:
-            extra.update(focal=hard[3], tversky=hard[4])
-    else:
-        _check_region_spec(hard_loss)
-        hard = torch.empty(REGION_VALS, device=dev, dtype=torch.float32)
-        _region_call(hard_loss, zs_c, zt_c, target, class_weights, ignore_index, T, alpha, None, hard, dzs)
-        extra = {"focal": hard[3], "tversky": hard[4]}
-    roots, grads = [zs], [dzs]
+    out = torch.empty(3, device=dev, dtype=torch.float32)         # the camera map's feature term, the LiDAR map's, the total
+    hard_term.call(hard_loss, zs_c, zt_c, target, class_weights, ignore_index, T, alpha, None, *bufs, dzs)
     gradsink.drop_pending()
-    if feature_loss is not None:
-        _check_feature_spec(feature_loss)
-        pair, ifv = isinstance(feature_loss, PairKD), isinstance(feature_loss, IntraClassKD)
-        names = ("pair_cam", "pair_lidar") if pair else ("ifv_cam", "ifv_lidar") if ifv else ("cwd_cam", "cwd_lidar")
-        tau = None if pair or ifv else float(feature_loss.tau)
-        for i, key in enumerate(("camera_feat", "lidar_feat")):
-            a, b = student_mids[key], teacher_mids[key]
-            if pair:
-                _check_pair_pair(a, b)
-            elif not ifv:
-                _check_cwd_pair(a, b)
-            am, geom = ops.nhwc_view(a.detach())
-            bm, _ = ops.nhwc_view(b.detach())
-            want = beta != 0.0 and a.requires_grad
-            da = torch.empty_like(am) if want else None
-            if pair:
-                gcoef = float(np.float32(_pair_gcoef(geom)) * np.float32(beta))             # the product the autograd form's backward forms
-                _pair_call(am, bm, geom, gcoef, None, vals[4 + i:5 + i], da)
-            elif ifv:
-                gcoef = float(np.float32(_ifv_gcoef(geom)) * np.float32(beta))              # the product the autograd form's backward forms
-                _ifv_call(am, bm, target, geom, NC, ignore_index, gcoef, None, vals[4 + i:5 + i], da)
-            else:
-                gcoef = float(np.float32(tau / (geom[0] * am.shape[1])) * np.float32(beta))     # the product the autograd form's backward forms
-                _cwd_call(am, bm, geom, tau, gcoef, None, vals[4 + i:5 + i], da)
-            if want:
-                gradsink.deposit(am, da)
-        lib.call("kd_kd_total", P(hard), P(vals[4:5]), P(vals[5:6]), float(alpha * T * T), float(beta), P(vals[6:7]), stream())
-        torch.autograd.backward(roots, grads)
-        if gradsink.pending():
-            gradsink.drop_pending()
-            raise KDError("kd_objective_backward: a feature-map gradient was not collected by the fusion block's backward "
-                          "(unsupported model structure for the fused objective; use kd_objective(...).backward())")
-        return vals[6], {"ce": hard[0], "kl": hard[1], names[0]: vals[4], names[1]: vals[5], **extra}
-    slabs, counts = [], []
-    for key in ("camera_feat", "lidar_feat"):
-        a, b = student_mids[key], teacher_mids[key]
-        am, _ = ops.nhwc_view(a.detach())
+    done = []
+    for i, (a, b) in enumerate(maps):
+        am, geom = ops.nhwc_view(a.detach())
         bm, _ = ops.nhwc_view(b.detach())
-        n = am.numel()
         want = beta != 0.0 and a.requires_grad
         da = torch.empty_like(am) if want else None
-        slab = torch.empty(lib.kd_mse_slab_blocks(n), device=dev, dtype=torch.float32)
-        gcoef = float(np.float32(2.0 / n) * np.float32(beta))      # the product autograd's fp32 chain rule forms
-        lib.call("kd_mse_partial", P(am), P(bm), n, gcoef, P(da), P(slab), stream())
-        slabs.append(slab)
-        counts.append(n)
+        done.append(feat.fused_map(feature_loss, am, bm, geom, target, NC, ignore_index, beta, out, i, da))
         if want:
             gradsink.deposit(am, da)
-    # the two MSE values and the total in one launch (vals[4], vals[5], vals[6])
-    lib.call("kd_kd_objective_final", P(hard), P(slabs[0]), counts[0], P(slabs[1]), counts[1], float(alpha * T * T), float(beta), P(vals[4:]),
-             stream())
-    torch.autograd.backward(roots, grads)
+    feat.fused_total(hard, out, done, float(alpha * T * T), float(beta))
+    torch.autograd.backward([zs], [dzs])
     if gradsink.pending():
         gradsink.drop_pending()
         raise KDError("kd_objective_backward: a feature-map gradient was not collected by the fusion block's backward "
                       "(unsupported model structure for the fused objective; use kd_objective(...).backward())")
-    return vals[6], {"ce": hard[0], "kl": hard[1], "mse_cam": vals[4], "mse_lidar": vals[5], **extra}
+    return out[2], {"ce": hard[0], "kl": hard[1], feat.parts[0]: out[0], feat.parts[1]: out[1],
+                    **hard_term.read(hard_loss, _FUSED, bufs, NC)}
 
 
 def confusion(logits, target, num_classes: int = 2, ignore_index: int = -1, out: Optional[torch.Tensor] = None):

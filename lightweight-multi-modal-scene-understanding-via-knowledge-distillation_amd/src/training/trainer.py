@@ -22,8 +22,7 @@ import torch.optim as optim
 from kdrt import gradsink
 from kdrt.ddp import BucketedAllReduce, broadcast_buffers, broadcast_module, distributed
 from kdrt.kd import KDStep
-from kdrt.lib import KDError
-from kdrt.losses import ChannelKD, IntraClassKD, LovaszLoss, OhemCE, PairKD, RegionLoss, confusion, lovasz_seg_loss, ohem_seg_loss, region_seg_loss, seg_loss
+from kdrt.losses import OhemCE, check_feature_loss, check_hard_classes, check_hard_loss, confusion, hard_seg_loss, seg_loss
 from kdrt.optim import AccumCycle, FusedAdamW, check_accum_steps, decay_groups
 
 try:
@@ -143,20 +142,12 @@ class Trainer(metaclass=_TakesNumClasses):
         # images (exact under data parallelism with equal shards); maps of at most 128 x 128 pixels.
         # hard_loss (kdrt.losses.OhemCE): the weighted CE over the mined pixels, 2 to 16 classes.  Mining is a training device:
         # validation reports the plain weighted CE.  Data parallel: each rank mines its own shard.
-        if hard_loss is not None and not isinstance(hard_loss, (RegionLoss, LovaszLoss, OhemCE)):
-            raise ValueError("hard_loss must be a kdrt.losses.RegionLoss, a kdrt.losses.LovaszLoss, a kdrt.losses.OhemCE or None, "
-                             f"got {type(hard_loss).__name__}")
+        check_hard_loss(hard_loss)
         self.hard_loss = hard_loss
+        self.criterion = lambda logits, seg: hard_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
         self.val_criterion = None                              # None: validate with the training criterion
-        if hard_loss is None:
-            self.criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
-        elif isinstance(hard_loss, OhemCE):
-            self.criterion = lambda logits, seg: ohem_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
+        if isinstance(hard_loss, OhemCE):
             self.val_criterion = lambda logits, seg: seg_loss(logits, seg, self.class_weights, self.ignore_index)[0]
-        elif isinstance(hard_loss, LovaszLoss):
-            self.criterion = lambda logits, seg: lovasz_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
-        else:
-            self.criterion = lambda logits, seg: region_seg_loss(logits, seg, self.hard_loss, self.class_weights, self.ignore_index)[0]
         # Parameter groups (no weight decay on BatchNorm parameters and biases, a learning-rate multiplier per top-level module)
         # and an EMA of the weights: all off by default, and the optimiser then makes exactly the calls it made before.  The
         # flat buffer keeps the model.parameters() order whatever the grouping, so the gradient buckets stay contiguous.
@@ -218,8 +209,7 @@ class Trainer(metaclass=_TakesNumClasses):
         if num_classes is not None:
             if self.class_weights is not None and self.class_weights.numel() != num_classes:
                 raise ValueError(f"class_weights has {self.class_weights.numel()} entries for num_classes={num_classes}")
-            if self.hard_loss is not None and not isinstance(self.hard_loss, OhemCE) and num_classes > 4:
-                raise KDError(f"hard_loss (RegionLoss / LovaszLoss) holds at most 4 classes, num_classes={num_classes}")
+            check_hard_classes(self.hard_loss, num_classes)
         self.num_classes = num_classes
         self.metric_classes = 2 if num_classes is None else num_classes
 
@@ -395,8 +385,7 @@ class KDTrainer(Trainer):
     student is broadcast from rank 0 and gradients are all-reduced in buckets overlapped with backward."""
 
     def __init__(self, model, teacher, train_loader, val_loader, device, T=4.0, alpha=1.0, beta=1.0, feature_loss=None, **kw):
-        if feature_loss is not None and not isinstance(feature_loss, (ChannelKD, PairKD, IntraClassKD)):
-            raise ValueError(f"feature_loss must be a kdrt.losses.ChannelKD, a kdrt.losses.PairKD, a kdrt.losses.IntraClassKD or None, got {type(feature_loss).__name__}")
+        check_feature_loss(feature_loss)
         super().__init__(model, train_loader, val_loader, device, **kw)
         self.teacher = teacher
         if distributed():
